@@ -17,14 +17,20 @@ bs=8, N=12288 points, 480x640, 4 encoder + 3 decoder fusion layers, one MI355X. 
 ranks every rank runs its own batch of 8 (weak scaling, no data-path collective: batch items
 are independent in the forward pass -- SURVEY.md section 8e); value = total frames / max-over-ranks time.
 
-The JSON line also carries
+A plain run sets up, warms up, times the K steps and prints the headline line (metric, value, unit, ms_per_step, ...).
+--dump-outputs DIR then writes what the last timed step computed as DIR/<name>.npy (float32 / float64, at most 64 MB in all);
+the inputs and weights are seeded, so two builds can be compared output for output.
+
+With --full the JSON line also carries (each costs runs of its own outside the timed steps, or events inside them)
   roofline      achieved algorithmic TFLOP/s (MFMA-bound launches) or GB/s (HBM-bound ones) of the dominant
                 hand-written kernel, measured live with HIP events on its launch stream during the timed steps
                 (which kernel that is, and hot_path_ops for all of them, come from untimed fully bracketed steps
                 between warm-up and the timed region);
   cpu_baseline  the CPU oracle path (reference nanoflann from oracle/_ref when present, else the
                 C restatement, + the plain-torch forward of oracle/forward_ref.py) timed on this
-                host's cores on a bounded sample (a few single frames).
+                host's cores on a bounded sample (a few single frames);
+and breakdown_ms, the KNN pair census, train_extra (>1 rank, training), the drop-in's operator table and plain-torch
+comparison (--path dropin), the serial schedule, network-vote variant and per-stage times (--mode e2e).
 """
 import argparse
 import json
@@ -50,6 +56,12 @@ def parse():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything beyond the headline figure (roofline, hot_path_ops, cpu_baseline, ...: see the "
+                         "module docstring); off: set up, warm up, time the steps, print the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed as DIR/<name>.npy (float32 / float64, "
+                         "at most 64 MB in all: a larger output is reduced to a fixed seeded sample of its elements)")
     ap.add_argument("--batch", type=int, default=None, help="frames per GPU per step (default: 8)")
     ap.add_argument("--n-points", type=int, default=None, help="points per frame (default: by --config)")
     ap.add_argument("--n-classes", type=int, default=22)
@@ -113,6 +125,8 @@ def parse():
                     help="A/B runs: set a boolean form attribute of ffb6d_amd.forward_pm (HEADS_SHARE_FIRST=0 ...) before the model is "
                          "built; the line's config.forms records what ran")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
     if args.batch is None:
         args.batch = 16 if args.config == 5 else 8
     if args.precision is None:
@@ -161,6 +175,29 @@ def state_dict(n_classes):
     with open(os.path.join(ROOT, "tests", "golden", "state_dict_keys.json")) as fh:
         shapes = json.load(fh)
     return synth.synth_state_dict_from_shapes(shapes, seed=0, n_classes=n_classes)
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(dirname, arrays):
+    """--dump-outputs: {name: tensor or array} -> dirname/<name>.npy, float64 for float64 and integer data, float32 for the
+    rest.  Past DUMP_LIMIT_BYTES in all, every array is reduced in the same proportion to a sample of its flattened elements
+    drawn with a fixed seed (the same positions on every run of the same arguments)."""
+    def host(v):
+        if isinstance(v, torch.Tensor):
+            v = v.detach()
+            v = (v.double() if v.dtype == torch.float64 or not v.is_floating_point() else v.float()).cpu().numpy()
+        v = np.asarray(v)
+        return v.astype(np.float64 if v.dtype == np.float64 or not np.issubdtype(v.dtype, np.floating) else np.float32)
+    arrays = {k: host(v) for k, v in arrays.items()}
+    total = sum(a.nbytes for a in arrays.values())
+    os.makedirs(dirname, exist_ok=True)
+    for name, a in arrays.items():
+        if total > DUMP_LIMIT_BYTES:
+            keep = int(a.size * DUMP_LIMIT_BYTES // total)
+            a = a.reshape(-1)[np.sort(np.random.RandomState(0).choice(a.size, keep, replace=False))]
+        np.save(os.path.join(dirname, name + ".npy"), a)
 
 
 def cpu_baseline(args, sd):
@@ -246,6 +283,8 @@ def run_e2e(args, dev, net, frames):
                               mesh_ctr=((rng.rand(n_cls, 3) - 0.5) * 0.02).astype(np.float32),
                               r_lst=(0.08 + 0.05 * rng.rand(n_cls - 1)).astype(np.float32)),
     }
+    if not args.full:       # the headline alone: synthetic votes, overlapped schedule
+        variants = {"synthetic_votes": variants["synthetic_votes"]}
     ev = lambda: torch.cuda.Event(enable_timing=True)                                     # noqa: E731
     out = {}
     K = args.steps
@@ -254,7 +293,7 @@ def run_e2e(args, dev, net, frames):
                                      pose_inputs=kw["pose_inputs"], seed=7)
         batches = [sensor] * K
         res = {}
-        for mode in ("serial", "overlapped"):
+        for mode in ("serial", "overlapped") if args.full else ("overlapped",):
             pipe.run([sensor] * max(2, args.warmup), overlap=mode == "overlapped")
             torch.cuda.synchronize()
             t0 = time.perf_counter()
@@ -263,6 +302,11 @@ def run_e2e(args, dev, net, frames):
             dt = time.perf_counter() - t0
             res[mode] = {"ms_per_batch": 1e3 * dt / K, "frames_per_s": B * K / dt}
             res[mode + "_objects_per_frame"] = float(np.mean([len(f[0]) for p in poses for f in p]))
+            if args.dump_outputs and name == "synthetic_votes" and mode == "overlapped":
+                dumped = {f"frame{b}_{key}": v for b, f in enumerate(poses[-1]) for key, v in zip(("class_ids", "poses", "kps"), f)}
+        if not args.full:
+            out[name] = res
+            continue
         # the three stages alone (HIP events / wall clock for the pose stage, which reads its results back)
         inp = pipe.assemble(sensor, 0)
         o = pipe.forward(inp)
@@ -287,6 +331,8 @@ def run_e2e(args, dev, net, frames):
         torch.cuda.synchronize()
         res["stage_ms"]["pose"] = 1e3 * (time.perf_counter() - t0) / 5
         out[name] = res
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, dumped)
     main = out["synthetic_votes"]
     line = {
         "metric": f"RGB-D frames/sec sensor->pose (480x640, N={N}, bs={B}, {n_obj} objects/frame)", "value": main["overlapped"]["frames_per_s"],
@@ -299,14 +345,15 @@ def run_e2e(args, dev, net, frames):
                                f"overlapped = input assembly of batch i+1 and pose solver of batch i on side streams under the forward of "
                                f"batch i+1 (ffb6d_amd/pipeline.py)"},
         "e2e": out,
-        "e2e_note": "synthetic_votes is the measured workload (5 objects per frame, ~1700 clustered votes per set).  network_votes feeds the "
-                    "random-init network's own outputs to the solver: one class for all 12288 points and offsets of ~80 m, i.e. one "
-                    "scattered 12288-vote set per frame whose points never meet -- max_iter + 1 rounds of 12288^2 pairs "
-                    "(profiles/r06_pose_netvotes_probe.txt); kept as the solver's worst case, not a pose workload",
         "reference_published": "57 ms forward + 18 ms pose = 75 ms per FRAME on the reference's GPU (README.md:305-330); other hardware, "
                                "not a baseline for vs_baseline",
         "roofline": None,
     }
+    if args.full:
+        line["e2e_note"] = ("synthetic_votes is the measured workload (5 objects per frame, ~1700 clustered votes per set).  network_votes feeds the "
+                            "random-init network's own outputs to the solver: one class for all 12288 points and offsets of ~80 m, i.e. one "
+                            "scattered 12288-vote set per frame whose points never meet -- max_iter + 1 rounds of 12288^2 pairs "
+                            "(profiles/r06_pose_netvotes_probe.txt); kept as the solver's worst case, not a pose workload")
     print(json.dumps(line), flush=True)
 
 
@@ -323,6 +370,8 @@ def run_dropin(args, dev, net, cld, dpt_xyz, fixed, idt):
         with torch.no_grad():
             return stand(inputs)
 
+    last = {}
+
     def timed(n):
         for _ in range(args.warmup):
             step()
@@ -330,15 +379,20 @@ def run_dropin(args, dev, net, cld, dpt_xyz, fixed, idt):
         a, b = ev(), ev()
         a.record()
         for _ in range(n):
-            step()
+            last["out"] = step()
         b.record()
         torch.cuda.synchronize()
         return a.elapsed_time(b) / n
 
-    plain_ms = timed(max(2, args.steps // 2))                 # unpatched: index expansion + torch.gather + permutes, softmax / mul / sum
+    if args.full:
+        plain_ms = timed(max(2, args.steps // 2))             # unpatched: index expansion + torch.gather + permutes, softmax / mul / sum
     undo = patch.patch_classes(dropin.FFB6D, dropin.Building_block, dropin.Att_pooling)
     try:
         ms = timed(args.steps)
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, last["out"])
+        if not args.full:
+            return print_dropin_line(args, ms, {"workload": DROPIN_WORKLOAD % (args.batch, args.n_points), "path": "dropin"})
         tr = _lib.Tracer(None)
         _lib.TRACER = tr
         for _ in range(3):
@@ -357,18 +411,25 @@ def run_dropin(args, dev, net, cld, dpt_xyz, fixed, idt):
                 if name in ("random_sample", "nearest_interpolation", "gather_neighbour", "relative_pos_encoding", "att_pool")}
     gathers = [k for k in ("random_sample", "nearest_interpolation", "gather_neighbour", "relative_pos_encoding", "att_pool") if k in table]
     dom = max(gathers, key=lambda k: table[k]["ms_per_step"])
-    line = {"metric": METRIC, "value": args.batch / (ms * 1e-3), "unit": "frames/s", "n_gpus": 1, "steps": args.steps, "warmup": args.warmup,
-            "ms_per_step": ms, "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
-            "config": {"workload": f"operator-level drop-in: on-device 22-call KNN index pyramid + the reference's forward dataflow in the "
-                                   f"reference's channel-major layout (stock conv / BatchNorm / activation modules, NCHW) with the five "
-                                   f"neighbour operators of ffb6d_amd.ops patched in (patch.patch_classes on ffb6d_amd/dropin.py); "
-                                   f"bs={args.batch}, N={args.n_points}, 480x640, fp32, one stream",
-                       "path": "dropin"},
-            "same_forward_with_plain_torch_operators": {"ms_per_step": plain_ms, "frames_per_s": args.batch / (plain_ms * 1e-3)},
-            "roofline": {"bound": "hbm", "achieved": table[dom]["algorithmic_GBps"], "peak": HBM_PEAK_GBS, "unit": "GB/s",
+    print_dropin_line(args, ms, {"workload": DROPIN_WORKLOAD % (args.batch, args.n_points), "path": "dropin"},
+               same_forward_with_plain_torch_operators={"ms_per_step": plain_ms, "frames_per_s": args.batch / (plain_ms * 1e-3)},
+               roofline={"bound": "hbm", "achieved": table[dom]["algorithmic_GBps"], "peak": HBM_PEAK_GBS, "unit": "GB/s",
                          "frac": table[dom]["frac_of_hbm_peak"], "traffic": None, "kernel": dom,
                          "note": "the drop-in operator with the largest share of the step; every operator: hot_path_ops / hot_path_ops_by_shape"},
-            "hot_path_ops": table, "hot_path_ops_by_shape": by_shape}
+               hot_path_ops=table, hot_path_ops_by_shape=by_shape)
+
+
+DROPIN_WORKLOAD = ("operator-level drop-in: on-device 22-call KNN index pyramid + the reference's forward dataflow in the "
+                   "reference's channel-major layout (stock conv / BatchNorm / activation modules, NCHW) with the five "
+                   "neighbour operators of ffb6d_amd.ops patched in (patch.patch_classes on ffb6d_amd/dropin.py); "
+                   "bs=%d, N=%d, 480x640, fp32, one stream")
+
+
+def print_dropin_line(args, ms, config, **extra):
+    """the --path dropin line: the headline fields, then what --full measured"""
+    line = {"metric": METRIC, "value": args.batch / (ms * 1e-3), "unit": "frames/s", "n_gpus": 1, "steps": args.steps, "warmup": args.warmup,
+            "ms_per_step": ms, "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
+            "config": config, **extra}
     print(json.dumps(line), flush=True)
 
 
@@ -535,60 +596,67 @@ def main():
             step()
         torch.cuda.synchronize()
 
-        # Untimed measurement passes between warm-up and the timed region (every rank runs them, to stay in step):
-        #  1. N_FULL steps in the benchmarked stream configuration with EVERY hand-written op bracketed by HIP events on
-        #     its launch stream -> hot_path_ops (with several streams an interval also counts the time a launch waits
-        #     behind the other streams' kernels);
-        #  2. the same steps on ONE stream: clean per-kernel durations -> which kernel is the dominant one, and
-        #     roofline.isolated.
-        # The timed region then brackets only the launches of that dominant kernel (two event records per launch are
-        # measurement overhead: ~180 launches per step cost ~3 % of a step when all of them are bracketed).
-        N_FULL = 3
-        full = _lib.Tracer(None if args.roofline_op == "auto" else [args.roofline_op])
-        _lib.TRACER = full
-        for _ in range(N_FULL):
-            step()
-        torch.cuda.synchronize()
-        _lib.TRACER = None
-        serial = None
-        pyramid_on_side = side is not None
-        if overlap:
-            net.two_streams, keep_side, side = False, side, None
-            serial = _lib.Tracer(None if args.roofline_op == "auto" else [args.roofline_op])
-            step()
-            torch.cuda.synchronize()
-            _lib.TRACER = serial
+        tracer = None
+        if args.full:
+            # Untimed measurement passes between warm-up and the timed region (every rank runs them, to stay in step):
+            #  1. N_FULL steps in the benchmarked stream configuration with EVERY hand-written op bracketed by HIP events on
+            #     its launch stream -> hot_path_ops (with several streams an interval also counts the time a launch waits
+            #     behind the other streams' kernels);
+            #  2. the same steps on ONE stream: clean per-kernel durations -> which kernel is the dominant one, and
+            #     roofline.isolated.
+            # The timed region then brackets only the launches of that dominant kernel (two event records per launch are
+            # measurement overhead: ~180 launches per step cost ~3 % of a step when all of them are bracketed).
+            N_FULL = 3
+            full = _lib.Tracer(None if args.roofline_op == "auto" else [args.roofline_op])
+            _lib.TRACER = full
             for _ in range(N_FULL):
                 step()
             torch.cuda.synchronize()
             _lib.TRACER = None
-            net.two_streams, side = True, keep_side
-        pyr_alone_ms = None
-        if pyramid_on_side:       # the pyramid by itself (it has no interval of its own inside a streamed step)
-            pe = [ev(), ev()]
-            pyramid.build_index_pyramid(cld, dpt_xyz, index_dtype=idt)
-            pe[0].record()
-            for _ in range(5):
+            serial = None
+            pyramid_on_side = side is not None
+            if overlap:
+                net.two_streams, keep_side, side = False, side, None
+                serial = _lib.Tracer(None if args.roofline_op == "auto" else [args.roofline_op])
+                step()
+                torch.cuda.synchronize()
+                _lib.TRACER = serial
+                for _ in range(N_FULL):
+                    step()
+                torch.cuda.synchronize()
+                _lib.TRACER = None
+                net.two_streams, side = True, keep_side
+            pyr_alone_ms = None
+            if pyramid_on_side:       # the pyramid by itself (it has no interval of its own inside a streamed step)
+                pe = [ev(), ev()]
                 pyramid.build_index_pyramid(cld, dpt_xyz, index_dtype=idt)
-            pe[1].record()
-            torch.cuda.synchronize()
-            pyr_alone_ms = pe[0].elapsed_time(pe[1]) / 5
+                pe[0].record()
+                for _ in range(5):
+                    pyramid.build_index_pyramid(cld, dpt_xyz, index_dtype=idt)
+                pe[1].record()
+                torch.cuda.synchronize()
+                pyr_alone_ms = pe[0].elapsed_time(pe[1]) / 5
 
-        split_mlp(full)
-        if serial is not None:
-            split_mlp(serial)
-        pick_from = (serial if serial is not None else full).summary()
-        cand = {k: v for k, v in pick_from.items() if not k.startswith("knn") and v["launches"] and k in full.records}
-        roof_op = args.roofline_op if args.roofline_op != "auto" else \
-            (max(cand, key=lambda k: cand[k]["total_ms"]) if cand else None)
-        tracer = _lib.Tracer(pred=lambda name, tag: roof_op is not None and split_name(name, tag) == roof_op)
+            split_mlp(full)
+            if serial is not None:
+                split_mlp(serial)
+            pick_from = (serial if serial is not None else full).summary()
+            cand = {k: v for k, v in pick_from.items() if not k.startswith("knn") and v["launches"] and k in full.records}
+            roof_op = args.roofline_op if args.roofline_op != "auto" else \
+                (max(cand, key=lambda k: cand[k]["total_ms"]) if cand else None)
+            tracer = _lib.Tracer(pred=lambda name, tag: roof_op is not None and split_name(name, tag) == roof_op)
+
+        region, last = [], {}
 
         def one_step(timed):
-            if timed and _lib.TRACER is None:
+            if timed and not region:
+                region.append(True)
                 if args.mark_region:
                     ops.check_index_range(marker, 1)
                 _lib.TRACER = tracer
-            step(record=timed)
+            out = step(record=timed and args.full)
+            if args.dump_outputs:
+                last["out"] = out
 
         elapsed = distributed.timed_steps(one_step, 0, args.steps, group, sync=torch.cuda.synchronize)
         _lib.TRACER = None
@@ -596,7 +664,7 @@ def main():
         # same steps on a second copy of the model with per-rank BatchNorm statistics (gradients the only collective) -- both variants
         # in one invocation, so that one run on the 8-GPU node prices SyncBatchNorm.
         train_extra = None
-        if train and world > 1:
+        if train and world > 1 and args.full:
             with distributed.count_collectives() as cc:
                 step()
                 torch.cuda.synchronize()
@@ -643,9 +711,46 @@ def main():
                 print("%-24s %-22s %5d %9.3f %9.1f %9.1f" % (name, str(tag), r["launches"], r["total_ms"], r["avg_us"],
                                                             r["gbps"]), file=sys.stderr)
 
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, last["out"])
     if rank == 0:
         ms_per_step = 1e3 * elapsed / args.steps
         value = args.batch * world * args.steps / elapsed
+        head = {
+            "metric": (METRIC.replace("12288", str(args.n_points)).replace("bs=8", "bs=%d" % args.batch)) if not train else
+                      f"RGB-D frames/sec train step (fwd+bwd+Adam, 480x640, N={args.n_points}, bs={args.batch}/GPU)",
+            "value": value, "unit": "frames/s", "n_gpus": world, "steps": args.steps,
+            "warmup": args.warmup, "ms_per_step": ms_per_step, "higher_is_better": True, "scaling": "weak",
+            "vs_baseline": None, "dtype": "bf16" if args.precision == "bf16" else "f32", "data": "synthetic",
+            "config": {"workload": ("FFB6D forward" if not train else "FFB6D training step (forward + backward + Adam, "
+                                    "train-mode BatchNorm with %s statistics, DDP gradient all-reduce when n_gpus > 1)" %
+                                    ("synchronised (SyncBatchNorm)" if not args.local_bn and world > 1 and args.dist_backend == "nccl" else "per-rank")) +
+                                   " incl. on-device 22-call KNN index pyramid; "
+                                   f"bs={args.batch}/GPU, N={args.n_points} pts, 480x640 RGB-D, "
+                                   f"{args.n_classes} classes, " + ("bf16 activations/weights with fp32 accumulation" if args.precision == "bf16" else "fp32") +
+                                   f", {'train' if train else 'eval'}" +
+                                   ((", objective: 2 * focal(gamma=2) + masked L1 offsets (train_lm.py:245-259) on synthetic targets"
+                                     if args.objective == "reference" else ", objective: mean of squared outputs (proxy)") if train else ""),
+                       "baseline_config": args.config, "global_batch": args.batch * world, "n_points": args.n_points,
+                       "index_dtype": args.index_dtype, "layout": "pm",
+                       # the forms a record was taken with (module attributes since round 4: no environment switches)
+                       "forms": {"lfa_fused": forward_pm.LFA_FUSED, "posenc_fused": forward_pm.POSENC_FUSED, "stem_fused": forward_pm.STEM_FUSED,
+                                 "last_stage_at_chosen": forward_pm.LAST_STAGE_AT_CHOSEN, "heads_share_first": forward_pm.HEADS_SHARE_FIRST, "heads_align_last": forward_pm.HEADS_ALIGN_LAST,
+                                 "heads_on_both_streams": forward_pm.HEADS_ON_BOTH_STREAMS, "heads_chain_fused": forward_pm.HEADS_CHAIN_FUSED,
+                                 "gemm_seq_form": forward_pm.GEMM_SEQ_FORM, "gemm_big_form": forward_pm.GEMM_BIG_FORM, "gemm_seq_lin": forward_pm.GEMM_SEQ_LIN, "gemm_seq_lin_one": forward_pm.GEMM_SEQ_LIN_ONE,
+                                 "miopen": ("find mode (cudnn.benchmark), " if args.cudnn_benchmark else "immediate mode, ") + miopen_db,
+                                 "upconv_fold": forward_pm.UPCONV_FOLD if isinstance(forward_pm.UPCONV_FOLD, str) else
+                                 (None if forward_pm.UPCONV_FOLD is None else sorted(forward_pm.UPCONV_FOLD)),
+                                 "upconv_fold_bf16": forward_pm.UPCONV_FOLD_BF16,
+                                 "psp_train_fold": model.PyramidPooling.fold_in_training,
+                                 "final_rows_log_softmax": model.FinalHead.rows_log_softmax, "upsample_rows": ops.UPSAMPLE_ROWS,
+                                 "pyramid_one_event": forward_pm.PYRAMID_ONE_EVENT},
+                       "parallelism": f"dp{world} (independent batches, one process per GPU, "
+                                      f"{args.dist_backend if world > 1 else 'no'} process group)"},
+        }
+    if rank == 0 and not args.full:
+        print(json.dumps(head), flush=True)
+    elif rank == 0:
         pyr_ms = float(np.mean([a.elapsed_time(b) for a, b in phase["pyramid"]]))
         fwd_ms = float(np.mean([a.elapsed_time(b) for a, b in phase["forward"]]))
         def is_gemm(name):
@@ -770,36 +875,7 @@ def main():
                 # 8 flop per pair (3 sub, 3 mul, 2 add) against the fp32 vector peak
                 "valu_frac_of_fp32_peak": evaluated * 8.0 / per_step_s / (VALU_PEAK_TFLOPS * 1e12)})
         line = {
-            "metric": (METRIC.replace("12288", str(args.n_points)).replace("bs=8", "bs=%d" % args.batch)) if not train else
-                      f"RGB-D frames/sec train step (fwd+bwd+Adam, 480x640, N={args.n_points}, bs={args.batch}/GPU)",
-            "value": value, "unit": "frames/s", "n_gpus": world, "steps": args.steps,
-            "warmup": args.warmup, "ms_per_step": ms_per_step, "higher_is_better": True, "scaling": "weak",
-            "vs_baseline": None, "dtype": "bf16" if args.precision == "bf16" else "f32", "data": "synthetic",
-            "config": {"workload": ("FFB6D forward" if not train else "FFB6D training step (forward + backward + Adam, "
-                                    "train-mode BatchNorm with %s statistics, DDP gradient all-reduce when n_gpus > 1)" %
-                                    ("synchronised (SyncBatchNorm)" if not args.local_bn and world > 1 and args.dist_backend == "nccl" else "per-rank")) +
-                                   " incl. on-device 22-call KNN index pyramid; "
-                                   f"bs={args.batch}/GPU, N={args.n_points} pts, 480x640 RGB-D, "
-                                   f"{args.n_classes} classes, " + ("bf16 activations/weights with fp32 accumulation" if args.precision == "bf16" else "fp32") +
-                                   f", {'train' if train else 'eval'}" +
-                                   ((", objective: 2 * focal(gamma=2) + masked L1 offsets (train_lm.py:245-259) on synthetic targets"
-                                     if args.objective == "reference" else ", objective: mean of squared outputs (proxy)") if train else ""),
-                       "baseline_config": args.config, "global_batch": args.batch * world, "n_points": args.n_points,
-                       "index_dtype": args.index_dtype, "layout": "pm",
-                       # the forms a record was taken with (module attributes since round 4: no environment switches)
-                       "forms": {"lfa_fused": forward_pm.LFA_FUSED, "posenc_fused": forward_pm.POSENC_FUSED, "stem_fused": forward_pm.STEM_FUSED,
-                                 "last_stage_at_chosen": forward_pm.LAST_STAGE_AT_CHOSEN, "heads_share_first": forward_pm.HEADS_SHARE_FIRST, "heads_align_last": forward_pm.HEADS_ALIGN_LAST,
-                                 "heads_on_both_streams": forward_pm.HEADS_ON_BOTH_STREAMS, "heads_chain_fused": forward_pm.HEADS_CHAIN_FUSED,
-                                 "gemm_seq_form": forward_pm.GEMM_SEQ_FORM, "gemm_big_form": forward_pm.GEMM_BIG_FORM, "gemm_seq_lin": forward_pm.GEMM_SEQ_LIN, "gemm_seq_lin_one": forward_pm.GEMM_SEQ_LIN_ONE,
-                                 "miopen": ("find mode (cudnn.benchmark), " if args.cudnn_benchmark else "immediate mode, ") + miopen_db,
-                                 "upconv_fold": forward_pm.UPCONV_FOLD if isinstance(forward_pm.UPCONV_FOLD, str) else
-                                 (None if forward_pm.UPCONV_FOLD is None else sorted(forward_pm.UPCONV_FOLD)),
-                                 "upconv_fold_bf16": forward_pm.UPCONV_FOLD_BF16,
-                                 "psp_train_fold": model.PyramidPooling.fold_in_training,
-                                 "final_rows_log_softmax": model.FinalHead.rows_log_softmax, "upsample_rows": ops.UPSAMPLE_ROWS,
-                                 "pyramid_one_event": forward_pm.PYRAMID_ONE_EVENT},
-                       "parallelism": f"dp{world} (independent batches, one process per GPU, "
-                                      f"{args.dist_backend if world > 1 else 'no'} process group)"},
+            **head,
             "breakdown_ms": ({"step": fwd_ms, "knn_pyramid_alone": pyr_alone_ms,
                               "note": "the forward builds the index pyramid itself (the 22 searches as two batches: K = 16, then K = 1) on a third HIP stream, "
                                       "under the network (forward_pm.StreamedPyramid); knn_pyramid_alone = the same 22 "

@@ -7,6 +7,7 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 pytestmark = pytest.mark.gpu
@@ -26,12 +27,26 @@ def _bench(*flags, timeout=420):
 
 
 def test_bench_spawns_two_ranks_and_reports_the_whole_job():
-    line = _bench("--gpus", "2", "--dist-backend", "gloo", "--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--cudnn-benchmark", "0")
+    line = _bench("--gpus", "2", "--dist-backend", "gloo", "--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--cudnn-benchmark", "0",
+                  "--full")
     assert line["n_gpus"] == 2 and line["config"]["global_batch"] == 16 and line["scaling"] == "weak"
     assert line["steps"] == 2 and line["warmup"] == 1 and line["unit"] == "frames/s"
     # whole-job aggregate: 16 frames per step over the slowest rank's time
     assert abs(line["value"] - 16 / (line["ms_per_step"] * 1e-3)) <= 1e-6 * line["value"]
     assert "roofline" in line and "gloo" in line["config"]["parallelism"]
+
+
+def test_plain_run_times_the_steps_and_dumps_the_last_outputs(tmp_path):
+    """a plain run's line holds the headline fields only; --dump-outputs writes the three end points of the last timed step"""
+    line = _bench("--steps", "3", "--warmup", "1", "--batch", "1", "--cudnn-benchmark", "0", "--dump-outputs", str(tmp_path))
+    assert line["steps"] == 3 and line["warmup"] == 1 and line["dtype"] == "f32" and line["higher_is_better"] is True
+    assert abs(line["value"] - 1 / (line["ms_per_step"] * 1e-3)) <= 1e-6 * line["value"]
+    assert not {"roofline", "hot_path_ops", "cpu_baseline", "breakdown_ms"} & set(line)
+    shapes = {"pred_rgbd_segs": (1, 22, 12288), "pred_kp_ofs": (1, 8, 12288, 3), "pred_ctr_ofs": (1, 1, 12288, 3)}
+    assert sorted(os.listdir(tmp_path)) == sorted(k + ".npy" for k in shapes)
+    for k, shape in shapes.items():
+        a = np.load(tmp_path / (k + ".npy"))
+        assert a.dtype == np.float32 and a.shape == shape and np.isfinite(a).all(), k
 
 
 def test_bench_spawns_eight_ranks_on_the_one_gpu():
@@ -49,7 +64,7 @@ def test_bench_train_mode_wraps_ddp_on_two_ranks():
     (Eight training ranks on one GPU were 173 s of MIOpen cold starts in the GPU suite; the eight-rank launch shape is covered by the
     inference test above, the gradient averaging by tests/test_multigpu_gpu.py and the gloo tests of tests/test_distributed_cpu.py.)"""
     line = _bench("--gpus", "2", "--dist-backend", "gloo", "--mode", "train", "--steps", "2", "--warmup", "1", "--no-cpu-baseline",
-                  "--batch", "1", "--cudnn-benchmark", "0", timeout=600)
+                  "--batch", "1", "--cudnn-benchmark", "0", "--full", timeout=600)
     assert line["n_gpus"] == 2 and line["config"]["global_batch"] == 2
     assert "train" in line["metric"] and line["value"] > 0
     # the per-step collective census every >1-rank training line carries (over gloo BatchNorm statistics stay per rank: no Python-side

@@ -1,5 +1,6 @@
 """ffb6d_amd/loss.py (the training objective bench.py --mode train times) against the reference's own loss module
-(ffb6d/models/loss.py, imported from /root/reference when present) and against hand-computed values; synthetic targets."""
+(ffb6d/models/loss.py: its terms and gradients recorded by tests/golden/make_golden_refcheck.py) and against hand-computed values;
+synthetic targets."""
 import importlib.util
 import os
 
@@ -7,46 +8,26 @@ import numpy as np
 import pytest
 import torch
 
+from conftest import GOLDEN
 from ffb6d_amd import loss, synth
 
-REF_LOSS = "/root/reference/ffb6d/models/loss.py"
+spec = importlib.util.spec_from_file_location("make_golden_refcheck", os.path.join(GOLDEN, "make_golden_refcheck.py"))
+refcheck = importlib.util.module_from_spec(spec)
+spec.loader.exec_module(refcheck)
 
 
-def case(seed, B=2, C=5, N=64, K=8):
-    g = torch.Generator().manual_seed(seed)
-    ep = {"pred_rgbd_segs": torch.randn(B, C, N, generator=g), "pred_kp_ofs": torch.randn(B, K, N, 3, generator=g),
-          "pred_ctr_ofs": torch.randn(B, 1, N, 3, generator=g)}
-    labels = torch.randint(0, C, (B, N), generator=g)
-    labels[0, : N // 2] = 0                                  # background points carry no offset loss
-    return ep, labels, torch.randn(B, N, K, 3, generator=g), torch.randn(B, N, 1, 3, generator=g)
-
-
-@pytest.mark.reference
-@pytest.mark.parametrize("seed", [0, 1])
+@pytest.mark.parametrize("seed", refcheck.LOSS_SEEDS)
 def test_objective_equals_the_reference_modules(seed):
-    spec = importlib.util.spec_from_file_location("ref_loss", REF_LOSS)
-    ref = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(ref)
-    ep, labels, kp_t, ctr_t = case(seed)
-    outs = []
-    for ours in (False, True):
-        leaves = {k: v.clone().requires_grad_(True) for k, v in ep.items()}
-        if ours:
-            total, terms = loss.training_loss(leaves, labels, kp_t, ctr_t)
-            terms = [terms["loss_rgbd_seg"], terms["loss_kp_of"], terms["loss_ctr_of"]]
-        else:                                                # train_lm.py:245-259 with criterion = FocalLoss(gamma=2), OFLoss()
-            import warnings
-            with warnings.catch_warnings():
-                warnings.simplefilter("ignore")              # F.log_softmax without dim (loss.py:31)
-                seg = ref.FocalLoss(gamma=2)(leaves["pred_rgbd_segs"], labels.view(-1)).sum()
-            kp = ref.OFLoss()(leaves["pred_kp_ofs"], kp_t, labels).sum()
-            ctr = ref.OFLoss()(leaves["pred_ctr_ofs"], ctr_t, labels).sum()
-            total, terms = 2.0 * seg + kp + ctr, [seg, kp, ctr]
-        total.backward()
-        outs.append(([float(t) for t in terms] + [float(total)], [leaves[k].grad for k in sorted(leaves)]))
-    np.testing.assert_allclose(outs[1][0], outs[0][0], rtol=1e-6, atol=1e-7)
-    for a, b in zip(outs[0][1], outs[1][1]):
-        torch.testing.assert_close(b, a, rtol=1e-5, atol=1e-7)
+    """train_lm.py:245-259 with criterion = FocalLoss(gamma=2), OFLoss(): 2 * seg + kp + ctr, terms and gradients"""
+    ep, labels, kp_t, ctr_t = refcheck.loss_case(seed)
+    ref = np.load(refcheck.LOSS_REF)
+    leaves = {k: v.clone().requires_grad_(True) for k, v in ep.items()}
+    total, terms = loss.training_loss(leaves, labels, kp_t, ctr_t)
+    total.backward()
+    got = [float(t) for t in (terms["loss_rgbd_seg"], terms["loss_kp_of"], terms["loss_ctr_of"], total)]
+    np.testing.assert_allclose(got, ref[f"s{seed}/terms"], rtol=1e-6, atol=1e-7)
+    for k in sorted(leaves):
+        torch.testing.assert_close(leaves[k].grad, torch.from_numpy(ref[f"s{seed}/grad/{k}"]), rtol=1e-5, atol=1e-7)
 
 
 def test_focal_term_by_hand_and_its_constant_modulating_factor():

@@ -45,7 +45,7 @@ def test_bench_two_gpus_over_rccl_inference():
 @two_gpus
 def test_bench_two_gpus_over_rccl_training_with_sync_batchnorm_in_bf16():
     line = _bench("--gpus", "2", "--mode", "train", "--precision", "bf16", "--steps", "3", "--warmup", "2", "--no-cpu-baseline",
-                  "--cudnn-benchmark", "0", timeout=1200)
+                  "--cudnn-benchmark", "0", "--full", timeout=1200)
     assert line["n_gpus"] == 2 and line["config"]["global_batch"] == 16
     assert "train" in line["metric"] and "SyncBatchNorm" in line["config"]["workload"] and line["value"] > 0
     # one invocation prices SyncBatchNorm: collectives of a step counted, the same steps timed with per-rank statistics as well

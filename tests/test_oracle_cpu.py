@@ -1,7 +1,8 @@
 """CPU suite: the oracle (our restatement of the reference algorithm) against the golden
-vectors produced by the reference itself, and -- where /root/reference exists -- against
-the reference's own compiled kd-tree."""
+vectors produced by the reference itself (its compiled kd-tree, its operators and its back-projection included:
+tests/golden/make_golden_refcheck.py)."""
 import hashlib
+import importlib.util
 import json
 import os
 
@@ -14,6 +15,10 @@ from ffb6d_amd import synth
 from oracle import knn as oknn
 from oracle import ops_ref
 from oracle import pyramid as opyr
+
+spec = importlib.util.spec_from_file_location("make_golden_refcheck", os.path.join(GOLDEN, "make_golden_refcheck.py"))
+refcheck = importlib.util.module_from_spec(spec)
+spec.loader.exec_module(refcheck)
 
 
 def sha(a):
@@ -98,68 +103,46 @@ def test_oracle_distance_pick_matches_reference_goldens():
         np.testing.assert_array_equal(q, z[name + "/queries"], err_msg=name)
 
 
-# ---- direct comparisons with the reference's own code (build container only) ------------
-@pytest.mark.reference
+# ---- bit-exact comparisons with the reference's own code, recorded by tests/golden/make_golden_refcheck.py ------------
 def test_oracle_distance_pick_equals_reference():
-    from oracle import ref_harness as rh
-    pts = np.random.RandomState(5).rand(2, 700, 3).astype(np.float32)
-    for seed in (1, 99991):
-        a = oknn.knn_batch_distance_pick(pts, 300, 16, seed)
-        b = rh.ref_knn_batch_distance_pick(pts, 300, 16, seed)
-        np.testing.assert_array_equal(a[0], b[0])
-        np.testing.assert_array_equal(a[1], b[1])
+    """the reference's cpp_knn_batch_distance_pick with its clock pinned (oracle/ref_shim.cpp): same K-NN and queries"""
+    pts = refcheck.pick_points()
+    want = refcheck.load_refcheck()["distance_pick"]
+    for seed in refcheck.PICK_SEEDS:
+        idx, queries = oknn.knn_batch_distance_pick(pts, 300, 16, seed)
+        assert idx.dtype == np.int64 and queries.dtype == np.float32
+        assert sha(idx) == want[str(seed)]["idx"] and sha(queries) == want[str(seed)]["queries"], seed
 
 
-@pytest.mark.reference
-@pytest.mark.parametrize("B,S,Q,K", [(1, 3000, 3000, 16), (2, 777, 1500, 1), (1, 4800, 48, 16), (1, 48, 4800, 1)])
+@pytest.mark.parametrize("B,S,Q,K", refcheck.KNN_CASES)
 def test_oracle_knn_equals_reference_kdtree(B, S, Q, K):
-    from oracle import ref_harness as rh
-    rng = np.random.RandomState(S + Q + K)
-    sup = rng.rand(B, S, 3).astype(np.float32)
-    qry = rng.rand(B, Q, 3).astype(np.float32)
-    np.testing.assert_array_equal(oknn.knn_batch(sup, qry, K), rh.ref_knn_batch(sup, qry, K, omp=True))
+    """the reference's nanoflann kd-tree (knn_.cxx, cpp_knn_batch_omp) on the same clouds: identical int64 indices"""
+    sup, qry = refcheck.knn_case(B, S, Q, K)
+    got = oknn.knn_batch(sup, qry, K)
+    assert got.dtype == np.int64 and got.shape == (B, Q, K)
+    assert sha(got) == refcheck.load_refcheck()["knn_batch"]["%d,%d,%d,%d" % (B, S, Q, K)]
 
 
-@pytest.mark.reference
 def test_ops_ref_equals_reference_functions():
-    from oracle import ref_harness as rh
-    m_ffb6d, m_randla, _ = rh.reference_modules()
-    g = torch.Generator().manual_seed(3)
-    feat = torch.randn(2, 7, 120, 1, generator=g)
-    pool = torch.randint(0, 120, (2, 33, 16), generator=g)
-    up = torch.randint(0, 120, (2, 500, 1), generator=g)
-    xyz = torch.rand(2, 120, 3, generator=g)
-    nei = torch.randint(0, 120, (2, 120, 16), generator=g)
-    assert torch.equal(ops_ref.random_sample(feat, pool), m_ffb6d.FFB6D.random_sample(feat, pool))
-    assert torch.equal(ops_ref.nearest_interpolation(feat, up), m_ffb6d.FFB6D.nearest_interpolation(feat, up))
-    pc = torch.randn(2, 120, 9, generator=g)
-    assert torch.equal(ops_ref.gather_neighbour(pc, nei), m_randla.Building_block.gather_neighbour(pc, nei))
-    bb = m_randla.Building_block(16)
-    assert torch.equal(ops_ref.relative_pos_encoding(xyz, nei), bb.relative_pos_encoding(xyz, nei))
+    """FFB6D.random_sample / nearest_interpolation, Building_block.gather_neighbour / relative_pos_encoding of the reference"""
+    feat, pool, up, xyz, nei, pc = refcheck.ops_case()
+    want = refcheck.load_refcheck()["ops"]
+    got = {"random_sample": ops_ref.random_sample(feat, pool), "nearest_interpolation": ops_ref.nearest_interpolation(feat, up),
+           "gather_neighbour": ops_ref.gather_neighbour(pc, nei), "relative_pos_encoding": ops_ref.relative_pos_encoding(xyz, nei)}
+    for name, t in got.items():
+        assert t.dtype == torch.float32 and sha(t.numpy()) == want[name], name
 
 
-@pytest.mark.reference
 def test_inputs_ref_equals_the_reference_dpt_2_pcld():
     """oracle/inputs_ref.dpt_2_pcld against the reference's own Dataset.dpt_2_pcld (linemod_dataset.py:188-199, called
     unbound on an object that carries the two index maps its __init__ builds, :31-32) followed by the NaN/Inf clean-up
     of get_item (:258-259): bit-identical, including invalid, NaN and Inf depth pixels and both intrinsics."""
-    import types
     from oracle import inputs_ref
-    from oracle import ref_harness as rh
-    Dataset = rh.reference_dataset_class()
-    me = types.SimpleNamespace(xmap=np.array([[j for i in range(640)] for j in range(480)]),
-                               ymap=np.array([[i for i in range(640)] for j in range(480)]))
-    rng = np.random.RandomState(3)
-    dpt = (1000.0 * (0.5 + rng.rand(480, 640))).astype(np.float32)
-    dpt[rng.rand(480, 640) < 0.1] = 0.0
-    dpt[7, 9], dpt[8, 10] = np.nan, np.inf
-    for K, cam_scale in ((synth.LINEMOD_K, 1000.0), (np.array([[1066.778, 0., 312.9869], [0., 1067.487, 241.3109], [0., 0., 1.]]), 10000.0)):
-        want = Dataset.dpt_2_pcld(me, dpt.copy(), cam_scale, K)
-        want[np.isnan(want)] = 0.0
-        want[np.isinf(want)] = 0.0
+    dpt, cams = refcheck.dpt_case()
+    for (K, cam_scale), want in zip(cams, refcheck.load_refcheck()["dpt_2_pcld"]):
         got = inputs_ref.dpt_2_pcld(dpt.copy(), cam_scale, K)
-        assert got.dtype == want.dtype
-        np.testing.assert_array_equal(got, want)
+        assert str(got.dtype) == want["dtype"] and list(got.shape) == want["shape"]
+        assert sha(got) == want["sha256"], cam_scale
 
 
 def test_depth_normal_restatement_recovers_plane_normals():

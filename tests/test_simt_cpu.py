@@ -562,20 +562,24 @@ def test_knn_on_the_emulator_tie_rule_on_quantised_clouds(emu):
     check()
 
 
-@pytest.mark.reference
 def test_knn_on_the_emulator_equals_the_reference_nanoflann(emu):
-    """the reference's knn_.cxx + nanoflann compiled in place (oracle/_ref) on the same clouds, tie runs canonicalised"""
+    """the reference's knn_.cxx + nanoflann (its output on the same clouds recorded by tests/golden/make_golden_refcheck.py),
+    tie runs canonicalised"""
+    import importlib.util
     import numpy as np
+    from conftest import GOLDEN
     from ffb6d_amd import nearest_neighbors as nn
     from oracle import knn as oknn
-    from oracle import ref_harness as rh
-    g = np.random.default_rng(3)
-    sup = g.standard_normal((2, 3500, 3)).astype(np.float32)
-    qry = g.standard_normal((2, 900, 3)).astype(np.float32)
+    spec = importlib.util.spec_from_file_location("make_golden_refcheck", os.path.join(GOLDEN, "make_golden_refcheck.py"))
+    refcheck = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(refcheck)
+    sup, qry = refcheck.emu_knn_case()
+    want = refcheck.load_refcheck()["emu_knn"]
     for K in (1, 16):
-        got, want = nn.knn_batch(sup, qry, K, omp=True), rh.ref_knn_batch(sup, qry, K, omp=True)
+        got = nn.knn_batch(sup, qry, K, omp=True)
         for b in range(sup.shape[0]):
-            np.testing.assert_array_equal(oknn.canonical_ties(got[b], sup[b], qry[b])[0], oknn.canonical_ties(want[b], sup[b], qry[b])[0])
+            canon = oknn.canonical_ties(got[b], sup[b], qry[b])[0]
+            assert canon.dtype == np.int64 and refcheck.sha(canon) == want[str(K)][b], (K, b)
 
 
 def test_distance_pick_on_the_emulator_matches_the_reference_goldens(emu, monkeypatch):
