@@ -98,6 +98,9 @@ SIGNATURES = {
     "ffb6d_set_labels_to_points": (_i32, [_vp, _vp, _vp, _vp, _i32, _i64, _i32, _vp, _vp]),
     "ffb6d_refine_mask_by_center": (_i32, [_vp, _vp, _vp, _i32, _vp, _vp, _vp, _vp, _i32, _i32, _vp, _vp]),
     "ffb6d_best_fit_transform_f32": (_i32, [_vp, _vp, _i32, _i32, _vp, _vp]),
+    # include/ffb6d_eval.h
+    "ffb6d_pose_add_adds_workspace_bytes": (_sz, [_i32, _i64]),
+    "ffb6d_pose_add_adds_f32": (_i32, [_vp, _vp, _i32, _vp, _vp, _vp, _i32, _vp, _vp, _vp, _sz, _vp]),
 }
 
 _LIB = None

@@ -248,3 +248,70 @@ def make_pose_case(seed, n_pts=2048, n_obj=2, n_kps=8, n_cls=None, noise=0.004, 
     mask[flip] = rng.randint(0, n_obj + 1, size=int(flip.sum()))
     return dict(pcld=pcld, mask=mask, ctr_of=ctr_of.astype(np.float32), kp_of=kp_of.astype(np.float32),
                 mesh_kps=mesh_kps, mesh_ctr=mesh_ctr, r_lst=r_lst, RT=RT)
+
+
+# ---- pose evaluation (ADD / ADD-S): model clouds and pose pairs ------------------------------------------------
+def model_cloud(seed, n_pts):
+    """An object-sized model cloud f32 [n_pts,3] (metres): an anisotropic blob of about 0.1 m."""
+    rng = np.random.RandomState(seed)
+    return (rng.randn(n_pts, 3) * [0.04, 0.025, 0.015]).astype(np.float32)
+
+
+def ring_model(seed, n_pts, k):
+    """A k-fold rotation-symmetric model f32 [n_pts,3] (n_pts divisible by k): n_pts / k seeded points and their copies
+    rotated by multiples of 2 pi / k about z, so rotating the model by `ring_angle(k)` maps it onto itself."""
+    rng = np.random.RandomState(seed)
+    base = np.stack([0.04 + 0.01 * rng.rand(n_pts // k), 0.002 * rng.randn(n_pts // k), 0.02 * rng.randn(n_pts // k)], 1)
+    return np.concatenate([base @ rot_z(j * ring_angle(k)).T for j in range(k)]).astype(np.float32)
+
+
+def ring_angle(k):
+    return 2.0 * np.pi / k
+
+
+def rot_z(a):
+    c, s = np.cos(a), np.sin(a)
+    return np.array([[c, -s, 0.0], [s, c, 0.0], [0.0, 0.0, 1.0]])
+
+
+def eval_pose_pair(seed, kind="near"):
+    """(pred f32 [3,4], gt f32 [3,4]) [R|t] pairs: kind = 'near' (a few degrees / centimetres off), 'far' (unrelated
+    poses), 'zero' (an all-zero prediction: the reference's undetected object) or 'same' (identical bits)."""
+    rng = np.random.RandomState(seed)
+    gt = np.zeros((3, 4))
+    gt[:, :3], gt[:, 3] = random_rotation(rng), [0.1 * rng.randn(), 0.1 * rng.randn(), 0.8 + 0.4 * rng.rand()]
+    if kind == "same":
+        pred = gt.copy()
+    elif kind == "zero":
+        pred = np.zeros((3, 4))
+    elif kind == "far":
+        pred = np.zeros((3, 4))
+        pred[:, :3], pred[:, 3] = random_rotation(rng), gt[:, 3] + 0.2 * rng.randn(3)
+    else:
+        axis = rng.randn(3)
+        axis /= np.linalg.norm(axis)
+        a = np.deg2rad(3.0 * rng.rand())
+        Kx = np.array([[0, -axis[2], axis[1]], [axis[2], 0, -axis[0]], [-axis[1], axis[0], 0]])
+        dR = np.eye(3) + np.sin(a) * Kx + (1 - np.cos(a)) * Kx @ Kx
+        pred = np.zeros((3, 4))
+        pred[:, :3], pred[:, 3] = dR @ gt[:, :3], gt[:, 3] + 0.01 * rng.randn(3)
+    return pred.astype(np.float32), gt.astype(np.float32)
+
+
+def pose_case_ground_truth(case, extra_seed=None):
+    """Ground truth of a make_pose_case frame in the layout of a YCB test batch: cls_ids i64 [n,1], RTs f32 [n,3,4],
+    gt_kps f32 [n,n_kps,3] (mesh keypoints under the true pose) for the objects 1..n_obj.  extra_seed: also one object
+    of class n_obj + 1 that no prediction has, then a row of class 0 (end of the list) and a row after it that the
+    evaluation must not reach."""
+    n_obj = int(case["mask"].max())
+    RT = case["RT"]
+    ids = list(range(1, n_obj + 1))
+    RTs = [RT[c] for c in ids]
+    kps = [case["mesh_kps"][c] @ RT[c, :, :3].T + RT[c, :, 3] for c in ids]
+    if extra_seed is not None:
+        _, gt = eval_pose_pair(extra_seed, "near")
+        ids += [n_obj + 1, 0, 1]
+        RTs += [gt, np.zeros((3, 4)), RT[1]]
+        kps += [kps[0] + 0.05, np.zeros_like(kps[0]), kps[0]]
+    return (np.asarray(ids, np.int64).reshape(-1, 1), np.asarray(RTs).astype(np.float32),
+            np.asarray(kps).astype(np.float32))
