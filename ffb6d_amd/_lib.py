@@ -101,6 +101,16 @@ SIGNATURES = {
     # include/ffb6d_eval.h
     "ffb6d_pose_add_adds_workspace_bytes": (_sz, [_i32, _i64]),
     "ffb6d_pose_add_adds_f32": (_i32, [_vp, _vp, _i32, _vp, _vp, _vp, _i32, _vp, _vp, _vp, _sz, _vp]),
+    # include/ffb6d_refine.h
+    "ffb6d_icp_prepared_bytes": (_sz, [_i64, _i32]),
+    "ffb6d_icp_prepare": (_i32, [_vp, _vp, _i32, _i64, _vp, _sz, _vp]),
+    "ffb6d_icp_workspace_bytes": (_sz, [_i32, _i64]),
+    "ffb6d_icp_set_form": (None, [_i32]),
+    "ffb6d_icp_set_pair_counter": (_i32, [_vp]),
+    "ffb6d_icp_correspond_f32": (_i32, [_vp, _i32, _i64, _vp, _vp, _i32, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i64, _c.c_float, _vp,
+                                        _vp, _vp, _vp, _sz, _vp]),
+    "ffb6d_icp_refine_f32": (_i32, [_vp, _i32, _i64, _vp, _vp, _i32, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i64, _c.c_float, _i32,
+                                    _c.c_double, _i32, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     # include/ffb6d_train.h
     "ffb6d_pose_targets": (_i32, [_vp, _vp, _i32, _vp, _i32, _vp, _vp, _i32, _vp, _vp, _i32, _i32, _i64, _i64, _i32, _i32, _vp,
                                   _vp, _vp, _vp, _vp, _vp, _vp, _vp]),

@@ -1,0 +1,663 @@
+// ffb6d_amd/csrc/icp.hip -- gfx950 ICP pose refinement (include/ffb6d_refine.h): point-to-point, scene -> model, every
+// (frame, object) pair of a batch in the same launches.  The reference repository has no ICP; the algorithm is stated in
+// the header and restated in numpy by tests/icp_ref.py.
+//
+// The model stays in its own frame: an iteration moves the SCENE points into it (q = R^T (s - t), 3 x 3 floats per problem),
+// so whatever is prepared on the model clouds -- Morton order, 64-point tiles, tile boxes -- serves every iteration, frame
+// and object.  Per call:
+//   icp_select_kernel      one workgroup per problem compacts its scene points (mask == class, keep) once, in index order
+//   icp_correspond_kernel  one workgroup per 64 scene points of a problem: nearest model point of each (exact fp32 distance,
+//                          ties to the lowest model index), the gate, and the block's 17 partial sums in double
+//                          (count, sum m, sum s, sum m s^T, sum d2) -- a fixed butterfly over the 64 lanes
+//   icp_solve_kernel       one workgroup per problem: the partial sums added in block order, Kabsch in double (csrc/kabsch.h,
+//                          the body of the keypoint fit), the bounding-box convergence test, the problem's state
+// A finished problem sets a flag that both kernels read first: no host polling, no read-back, the call never waits.
+//
+// Two forms of the search, identical results (the comparison is on (d2 bits, model index) as one 64-bit key, and a tile is
+// skipped only when its box is STRICTLY farther than the best distance; the box distance is rounded like the point distance,
+// so it never exceeds the distance of a point inside the box):
+//   scan    lane = scene point; the class's cloud streams through LDS in 1024-point chunks, the four wavefronts take the
+//           chunk's tiles in turn (same-address LDS reads: broadcast) and meet in LDS
+//   pruned  wavefront = one scene point at a time, lane = model point of a tile: the lanes first measure the tile boxes
+//           (64 boxes per step), the nearest box is visited first, then only the boxes that are not farther than the best
+//           distance so far.  The skip test is wave-uniform by construction, so it pays although neighbouring scene points
+//           of a block lie anywhere on the object (they are in cloud order).
+#include <algorithm>
+#include <cmath>
+#include <limits>
+#include <vector>
+
+#include "common.h"
+#include "ffb6d_refine.h"
+#include "kabsch.h"
+
+namespace {
+
+using ffb6d::ceil_div;
+
+constexpr int kBlock = 256;
+constexpr int kTilePts = 64;                  // scene points per workgroup = model points per tile = lanes
+constexpr int kChunk = 1024;                  // model points in LDS per step of the scan form (16 KB)
+constexpr int kSums = 17;                     // count, sum m (3), sum s (3), sum m s^T (9), sum d2
+constexpr int kPrunedMin = 1024;              // form -1 (automatic): classes of at least this many points take the pruned form
+constexpr int kNoIndex = 0x7fffffff;
+constexpr unsigned long long kNoKey = (0x7f800000ull << 32) | 0x7fffffffull;      // (+inf, no index): loses against every point
+
+struct ClassInfo { int pt_begin, count, tile_begin, n_tiles; };
+
+struct Prepared {
+    const ClassInfo* cls;                     // [n_cls]
+    const float4* cls_lo;                     // [n_cls] bounding box of the class
+    const float4* cls_hi;
+    const float4* orig;                       // [total] the clouds in their own order
+    const float4* sorted;                     // [max_tiles * 64] {x, y, z, index within the class}, Morton order, NaN padding
+    const float4* tile_lo;                    // [max_tiles]
+    const float4* tile_hi;
+};
+
+size_t align256(size_t x) { return (x + 255) & ~static_cast<size_t>(255); }
+
+struct Layout { size_t cls, cls_box, orig, sorted, tile_box, bytes; int64_t max_tiles; };
+
+Layout prepared_layout(int64_t total, int n_cls) {
+    Layout l;
+    l.max_tiles = total / kTilePts + n_cls;   // >= sum over the classes of ceil(count / 64)
+    l.cls = 0;
+    l.cls_box = l.cls + align256(sizeof(ClassInfo) * n_cls);
+    l.orig = l.cls_box + align256(2 * sizeof(float4) * n_cls);
+    l.sorted = l.orig + align256(sizeof(float4) * static_cast<size_t>(total));
+    l.tile_box = l.sorted + align256(sizeof(float4) * static_cast<size_t>(l.max_tiles) * kTilePts);
+    l.bytes = l.tile_box + align256(2 * sizeof(float4) * static_cast<size_t>(l.max_tiles));
+    return l;
+}
+
+Prepared prepared_view(const void* base, const Layout& l, int n_cls) {
+    const char* b = static_cast<const char*>(base);
+    Prepared m;
+    m.cls = reinterpret_cast<const ClassInfo*>(b + l.cls);
+    m.cls_lo = reinterpret_cast<const float4*>(b + l.cls_box);
+    m.cls_hi = m.cls_lo + n_cls;
+    m.orig = reinterpret_cast<const float4*>(b + l.orig);
+    m.sorted = reinterpret_cast<const float4*>(b + l.sorted);
+    m.tile_lo = reinterpret_cast<const float4*>(b + l.tile_box);
+    m.tile_hi = m.tile_lo + l.max_tiles;
+    return m;
+}
+
+// ---- the arithmetic the header states, every operation rounded on its own -----------------------------------------
+__device__ __forceinline__ float dist2(float qx, float qy, float qz, float mx, float my, float mz) {
+    const float dx = __fsub_rn(qx, mx), dy = __fsub_rn(qy, my), dz = __fsub_rn(qz, mz);
+    return __fadd_rn(__fadd_rn(__fmul_rn(dx, dx), __fmul_rn(dy, dy)), __fmul_rn(dz, dz));
+}
+
+// lower bound of dist2 over the points of a box: per axis fl(lo - q) <= fl(p - q) for p >= lo (rounding is monotone), and
+// squares and sums of non-negative terms keep the order.  A NaN coordinate gives 0 (the tile is visited).
+__device__ __forceinline__ float box_dist2(float qx, float qy, float qz, const float4 lo, const float4 hi) {
+    const float ex = fmaxf(fmaxf(__fsub_rn(lo.x, qx), __fsub_rn(qx, hi.x)), 0.f);
+    const float ey = fmaxf(fmaxf(__fsub_rn(lo.y, qy), __fsub_rn(qy, hi.y)), 0.f);
+    const float ez = fmaxf(fmaxf(__fsub_rn(lo.z, qz), __fsub_rn(qz, hi.z)), 0.f);
+    return __fadd_rn(__fadd_rn(__fmul_rn(ex, ex), __fmul_rn(ey, ey)), __fmul_rn(ez, ez));
+}
+
+// distances are >= +0 or NaN: their order is the order of their bits, NaN above +inf
+__device__ __forceinline__ unsigned long long make_key(float d2, float index_bits) {
+    return (static_cast<unsigned long long>(__float_as_uint(d2)) << 32) | static_cast<unsigned long long>(__float_as_uint(index_bits));
+}
+
+__device__ __forceinline__ unsigned long long wave_min_key(unsigned long long v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        const unsigned long long other = __shfl_xor(v, o);
+        v = other < v ? other : v;
+    }
+    return v;
+}
+
+__device__ __forceinline__ double shfl_xor_f64(double v, int o) {
+    return __builtin_bit_cast(double, __shfl_xor(__builtin_bit_cast(unsigned long long, v), o));
+}
+
+__device__ __forceinline__ unsigned long long visit_tile(const float4* __restrict__ sorted, int t, int lane, float qx, float qy, float qz) {
+    const float4 m = sorted[static_cast<int64_t>(t) * kTilePts + lane];
+    return wave_min_key(make_key(dist2(qx, qy, qz, m.x, m.y, m.z), m.w));
+}
+
+// ---- scene sets ------------------------------------------------------------------------------------------------------
+template <typename MaskT>
+__global__ __launch_bounds__(kBlock) void icp_select_kernel(
+    const float* __restrict__ pcld, const MaskT* __restrict__ mask, const unsigned char* __restrict__ keep,
+    const int* __restrict__ frame_of, const int* __restrict__ class_of, int B, int N, int64_t stride, float4* __restrict__ sets,
+    int* __restrict__ counts) {
+    __shared__ int wave_total[kBlock / 64];
+    const int p = blockIdx.x;
+    const int b = frame_of[p];
+    if (b < 0 || b >= B) {                                      // never an index: a problem without scene points
+        if (threadIdx.x == 0) counts[p] = 0;
+        return;
+    }
+    const MaskT cls = static_cast<MaskT>(class_of[p]);
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    int base = 0;
+    for (int i0 = 0; i0 < N; i0 += kBlock) {
+        const int i = i0 + threadIdx.x;
+        bool sel = false;
+        if (i < N) sel = mask[static_cast<int64_t>(b) * N + i] == cls && (!keep || keep[static_cast<int64_t>(b) * N + i]);
+        const unsigned long long bal = __ballot(sel);
+        const int before = __popcll(bal & ((1ull << lane) - 1ull));
+        __syncthreads();
+        if (lane == 0) wave_total[wave] = __popcll(bal);
+        __syncthreads();
+        int pos = base + before, total = 0;
+#pragma unroll
+        for (int w = 0; w < kBlock / 64; ++w) {
+            if (w < wave) pos += wave_total[w];
+            total += wave_total[w];
+        }
+        if (sel) {
+            const float* pt = pcld + (static_cast<int64_t>(b) * N + i) * 3;
+            sets[static_cast<int64_t>(p) * stride + pos] = make_float4(pt[0], pt[1], pt[2], __int_as_float(i));
+        }
+        base += total;
+    }
+    if (threadIdx.x == 0) counts[p] = base;
+}
+
+__global__ __launch_bounds__(kBlock) void icp_fill_kernel(int* __restrict__ idx, float* __restrict__ d2, int64_t n) {
+    const int64_t i = static_cast<int64_t>(blockIdx.x) * kBlock + threadIdx.x;
+    if (i >= n) return;
+    if (idx) idx[i] = -1;
+    if (d2) d2[i] = __uint_as_float(0x7f800000u);
+}
+
+// ---- correspondences + partial sums -------------------------------------------------------------------------------
+struct CorrArgs {
+    const float4* sets;
+    const int* counts;
+    int64_t stride;
+    const int* class_of;
+    const double* T;
+    const int* done;                          // or NULL
+    Prepared m;
+    int n_cls;
+    float max_d2;
+    int form;
+    int* idx_out;                             // or NULL
+    float* d2_out;                            // or NULL
+    double* partials;                         // or NULL
+    int tiles;                                // blocks per problem in `partials`
+    unsigned long long* pairs;                // or NULL
+};
+
+__global__ __launch_bounds__(kBlock) void icp_correspond_kernel(const CorrArgs a) {
+    __shared__ float4 chunk[kChunk];
+    __shared__ float4 qs[kTilePts];
+    __shared__ unsigned long long wkey[kBlock / 64][kTilePts];
+    const int p = blockIdx.y, tile = blockIdx.x;
+    if (a.done && a.done[p]) return;
+    const int cnt = a.counts[p];
+    const int q0 = tile * kTilePts;
+    if (q0 >= cnt) return;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int cls = a.class_of[p];
+    ClassInfo ci = {0, 0, 0, 0};
+    if (cls >= 0 && cls < a.n_cls) ci = a.m.cls[cls];           // (a class id that is no index: no model points)
+    float Rt[12];
+#pragma unroll
+    for (int k = 0; k < 12; ++k) Rt[k] = static_cast<float>(a.T[static_cast<int64_t>(p) * 12 + k]);
+    const float4 s = a.sets[static_cast<int64_t>(p) * a.stride + min(q0 + lane, cnt - 1)];
+    // q = R^T (s - t)
+    const float d0 = __fsub_rn(s.x, Rt[3]), d1 = __fsub_rn(s.y, Rt[7]), d2s = __fsub_rn(s.z, Rt[11]);
+    const float qx = __fadd_rn(__fadd_rn(__fmul_rn(d0, Rt[0]), __fmul_rn(d1, Rt[4])), __fmul_rn(d2s, Rt[8]));
+    const float qy = __fadd_rn(__fadd_rn(__fmul_rn(d0, Rt[1]), __fmul_rn(d1, Rt[5])), __fmul_rn(d2s, Rt[9]));
+    const float qz = __fadd_rn(__fadd_rn(__fmul_rn(d0, Rt[2]), __fmul_rn(d1, Rt[6])), __fmul_rn(d2s, Rt[10]));
+    const float4* __restrict__ sorted = a.m.sorted + static_cast<int64_t>(ci.tile_begin) * kTilePts;
+    const int n_valid = min(kTilePts, cnt - q0);
+    const bool pruned = a.form == 1 || (a.form < 0 && ci.count >= kPrunedMin);
+    unsigned long long wave_pairs = 0;
+
+    if (!pruned) {
+        unsigned long long best = kNoKey;
+        const int n_pad = ci.n_tiles * kTilePts;
+        const float nanf_ = __uint_as_float(0x7fc00000u);
+        for (int j0 = 0; j0 < n_pad; j0 += kChunk) {
+            __syncthreads();
+            for (int x = tid; x < kChunk; x += kBlock) {
+                const int j = j0 + x;
+                chunk[x] = j < n_pad ? sorted[j] : make_float4(nanf_, nanf_, nanf_, __int_as_float(kNoIndex));
+            }
+            __syncthreads();
+            const int n = min(kChunk, n_pad - j0);
+            for (int x0 = wave * kTilePts; x0 < n; x0 += kBlock) {
+#pragma unroll 8
+                for (int k = 0; k < kTilePts; ++k) {
+                    const float4 m = chunk[x0 + k];
+                    const unsigned long long key = make_key(dist2(qx, qy, qz, m.x, m.y, m.z), m.w);
+                    best = key < best ? key : best;
+                }
+                wave_pairs += static_cast<unsigned long long>(kTilePts) * n_valid;
+            }
+        }
+        wkey[wave][lane] = best;
+        __syncthreads();
+        if (wave == 0) {
+#pragma unroll
+            for (int w = 1; w < kBlock / 64; ++w) best = wkey[w][lane] < best ? wkey[w][lane] : best;
+            wkey[0][lane] = best;
+        }
+    } else {
+        if (wave == 0) qs[lane] = make_float4(qx, qy, qz, 0.f);
+        __syncthreads();
+        const int T = ci.n_tiles;
+        const float4* __restrict__ tlo = a.m.tile_lo + ci.tile_begin;
+        const float4* __restrict__ thi = a.m.tile_hi + ci.tile_begin;
+        constexpr int kPer = kTilePts / (kBlock / 64);          // scene points per wavefront
+        for (int i = 0; i < kPer; ++i) {
+            const int pi = wave * kPer + i;
+            if (pi >= n_valid) break;
+            const float4 qq = qs[pi];
+            unsigned long long bk = kNoKey;
+            if (T > 0) {
+                unsigned long long near = ~0ull;
+                for (int g = 0; g < T; g += 64) {
+                    const int t = g + lane;
+                    if (t < T) {
+                        const unsigned long long k = (static_cast<unsigned long long>(__float_as_uint(box_dist2(qq.x, qq.y, qq.z, tlo[t], thi[t]))) << 32) | static_cast<unsigned>(t);
+                        near = k < near ? k : near;
+                    }
+                }
+                near = wave_min_key(near);
+                const int t_first = static_cast<int>(near & 0xffffffffull);
+                bk = visit_tile(sorted, t_first, lane, qq.x, qq.y, qq.z);
+                wave_pairs += kTilePts;
+                for (int g = 0; g < T; g += 64) {
+                    const int t = g + lane;
+                    float bd = 0.f;
+                    bool cand = false;
+                    if (t < T && t != t_first) {
+                        bd = box_dist2(qq.x, qq.y, qq.z, tlo[t], thi[t]);
+                        cand = !(bd > __uint_as_float(static_cast<unsigned>(bk >> 32)));
+                    }
+                    unsigned long long todo = __ballot(cand);
+                    while (todo) {
+                        const int l = __ffsll(static_cast<long long>(todo)) - 1;
+                        todo &= todo - 1;
+                        if (__shfl(bd, l, 64) > __uint_as_float(static_cast<unsigned>(bk >> 32))) continue;      // the best has improved since
+                        const unsigned long long k = visit_tile(sorted, g + l, lane, qq.x, qq.y, qq.z);
+                        bk = k < bk ? k : bk;
+                        wave_pairs += kTilePts;
+                    }
+                }
+            }
+            if (lane == 0) wkey[0][pi] = bk;
+        }
+        __syncthreads();
+    }
+    if (a.pairs && lane == 0 && wave_pairs) atomicAdd(a.pairs, wave_pairs);
+    if (wave != 0) return;
+
+    // the gate, the outputs of the single step, the block's sums
+    const bool valid = lane < n_valid;
+    const unsigned long long key = valid ? wkey[0][lane] : kNoKey;
+    const int idx = static_cast<int>(key & 0xffffffffull);
+    float d2 = __uint_as_float(static_cast<unsigned>(key >> 32));
+    const bool matched = idx != kNoIndex;
+    if (!matched) d2 = ci.count > 0 ? __uint_as_float(0x7fc00000u) : __uint_as_float(0x7f800000u);   // every distance NaN / no model
+    if (d2 != d2) d2 = __uint_as_float(0x7fc00000u);
+    const bool kept = valid && matched && d2 <= a.max_d2;       // (false for NaN)
+    if (valid) {
+        const int64_t at = static_cast<int64_t>(p) * a.stride + q0 + lane;
+        if (a.idx_out) a.idx_out[at] = kept ? idx : -1;
+        if (a.d2_out) a.d2_out[at] = d2;
+    }
+    if (!a.partials) return;
+    double v[kSums];
+#pragma unroll
+    for (int k = 0; k < kSums; ++k) v[k] = 0.0;
+    if (kept) {
+        const float4 m = a.m.orig[ci.pt_begin + idx];
+        const double mm[3] = {m.x, m.y, m.z}, ss[3] = {s.x, s.y, s.z};
+        v[0] = 1.0;
+#pragma unroll
+        for (int r = 0; r < 3; ++r) {
+            v[1 + r] = mm[r];
+            v[4 + r] = ss[r];
+#pragma unroll
+            for (int c = 0; c < 3; ++c) v[7 + 3 * r + c] = mm[r] * ss[c];
+        }
+        v[16] = d2;
+    }
+#pragma unroll
+    for (int k = 0; k < kSums; ++k) {
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) v[k] += shfl_xor_f64(v[k], o);
+    }
+    if (lane == 0) {
+        double* out = a.partials + (static_cast<int64_t>(p) * a.tiles + tile) * kSums;
+#pragma unroll
+        for (int k = 0; k < kSums; ++k) out[k] = v[k];
+    }
+}
+
+// ---- the update -----------------------------------------------------------------------------------------------------
+struct SolveArgs {
+    const int* counts;
+    const int* class_of;
+    Prepared m;
+    int n_cls;
+    const double* partials;
+    int tiles;
+    double* T;
+    int* done;
+    int* iters;
+    int* n_pairs;
+    float* rms;
+    int min_pairs;
+    double tol;
+};
+
+__global__ __launch_bounds__(64) void icp_solve_kernel(const SolveArgs a) {
+    __shared__ double sh[kSums];
+    const int p = blockIdx.x;
+    if (a.done[p]) return;
+    const int nt = (a.counts[p] + kTilePts - 1) / kTilePts;
+    const int k = threadIdx.x;
+    if (k < kSums) {
+        double s = 0.0;
+        for (int t = 0; t < nt; ++t) s += a.partials[(static_cast<int64_t>(p) * a.tiles + t) * kSums + k];      // block order
+        sh[k] = s;
+    }
+    __syncthreads();
+    if (k != 0) return;
+    const double n = sh[0];
+    a.n_pairs[p] = static_cast<int>(n);
+    a.rms[p] = n > 0 ? static_cast<float>(sqrt(sh[16] / n)) : 0.f;
+    if (n < static_cast<double>(a.min_pairs)) {                 // too few pairs: the pose stays, the problem is over
+        a.done[p] = 1;
+        return;
+    }
+    double ca[3], cb[3], H[3][3];
+    for (int r = 0; r < 3; ++r) {
+        ca[r] = sh[1 + r] / n;
+        cb[r] = sh[4 + r] / n;
+    }
+    for (int r = 0; r < 3; ++r)
+        for (int c = 0; c < 3; ++c) H[r][c] = sh[7 + 3 * r + c] - n * ca[r] * cb[c];      // sum (m - ca)(s - cb)^T
+    double Tn[12];
+    ffb6d::kabsch_from_covariance(H, ca, cb, Tn);
+    double* To = a.T + static_cast<int64_t>(p) * 12;
+    bool conv = false;
+    const int cls = a.class_of[p];
+    if (a.tol > 0 && cls >= 0 && cls < a.n_cls) {
+        const float4 lo = a.m.cls_lo[cls], hi = a.m.cls_hi[cls];
+        double mv = 0.0;
+        for (int c8 = 0; c8 < 8; ++c8) {
+            const double x = (c8 & 1) ? hi.x : lo.x, y = (c8 & 2) ? hi.y : lo.y, z = (c8 & 4) ? hi.z : lo.z;
+            double e2 = 0.0;
+            for (int r = 0; r < 3; ++r) {
+                const double dn = Tn[4 * r] * x + Tn[4 * r + 1] * y + Tn[4 * r + 2] * z + Tn[4 * r + 3];
+                const double dp = To[4 * r] * x + To[4 * r + 1] * y + To[4 * r + 2] * z + To[4 * r + 3];
+                e2 += (dn - dp) * (dn - dp);
+            }
+            mv = fmax(mv, sqrt(e2));
+        }
+        conv = mv <= a.tol;
+    }
+    for (int i = 0; i < 12; ++i) To[i] = Tn[i];
+    a.iters[p] += 1;
+    if (conv) a.done[p] = 1;
+}
+
+// ---- host ------------------------------------------------------------------------------------------------------------
+struct Workspace {
+    float4* sets;
+    int* counts;
+    double* partials;
+    double* T;
+    int *done, *iters, *n_pairs;
+    float* rms;
+    int tiles;
+    size_t state_off, state_bytes, bytes;
+};
+
+Workspace workspace_layout(void* base, int P, int64_t set_stride) {
+    Workspace w;
+    char* b = static_cast<char*>(base);
+    w.tiles = static_cast<int>(ceil_div(set_stride, kTilePts));
+    size_t off = 0;
+    w.sets = reinterpret_cast<float4*>(b + off);
+    off += align256(sizeof(float4) * static_cast<size_t>(P) * set_stride);
+    w.counts = reinterpret_cast<int*>(b + off);
+    off += align256(sizeof(int) * P);
+    w.partials = reinterpret_cast<double*>(b + off);
+    off += align256(sizeof(double) * kSums * static_cast<size_t>(P) * w.tiles);
+    w.T = reinterpret_cast<double*>(b + off);
+    off += align256(sizeof(double) * 12 * P);
+    w.state_off = off;
+    w.done = reinterpret_cast<int*>(b + off);
+    w.iters = w.done + P;
+    w.n_pairs = w.iters + P;
+    w.rms = reinterpret_cast<float*>(w.n_pairs + P);
+    w.state_bytes = 4 * sizeof(int) * P;
+    off += align256(w.state_bytes);
+    w.bytes = off;
+    return w;
+}
+
+int g_form = 0;                               // scan until the pruned form is measured faster at both model sizes
+unsigned long long* g_pairs = nullptr;
+
+unsigned morton10(unsigned x, unsigned y, unsigned z) {
+    auto spread = [](unsigned v) {
+        v &= 0x3ffu;
+        v = (v | (v << 16)) & 0x030000ffu;
+        v = (v | (v << 8)) & 0x0300f00fu;
+        v = (v | (v << 4)) & 0x030c30c3u;
+        v = (v | (v << 2)) & 0x09249249u;
+        return v;
+    };
+    return spread(x) | (spread(y) << 1) | (spread(z) << 2);
+}
+
+int check_scene_args(const char* who, const void* prepared, int n_cls, int64_t total, const void* pcld, const void* mask, int mask_bits,
+                     const int* frame_of, const int* class_of, const double* T, int P, int B, int N, int64_t set_stride, float max_dist,
+                     void* workspace, size_t workspace_bytes) {
+    FFB6D_REQUIRE(P >= 0 && P <= 65535 && B > 0 && N > 0 && n_cls > 0 && total >= 0, "%s: bad sizes P=%d B=%d N=%d n_cls=%d total=%lld", who, P, B, N, n_cls,
+                  (long long)total);
+    FFB6D_REQUIRE(mask_bits == 32 || mask_bits == 64, "%s: mask_bits must be 32 or 64, got %d", who, mask_bits);
+    FFB6D_REQUIRE(set_stride >= N, "%s: set_stride %lld < N %d", who, (long long)set_stride, N);
+    FFB6D_REQUIRE(max_dist > 0.f, "%s: max_dist must be positive (inf allowed), got %g", who, (double)max_dist);
+    if (P == 0) return 0;
+    FFB6D_REQUIRE(prepared && pcld && mask && frame_of && class_of && T, "%s: null pointer", who);
+    const size_t need = ffb6d_icp_workspace_bytes(P, set_stride);
+    if (!workspace || workspace_bytes < need)
+        return ffb6d::set_error(FFB6D_ERR_WORKSPACE, "%s: workspace %zu < %zu bytes", who, workspace_bytes, need);
+    return 0;
+}
+
+int launch_select(const float* pcld, const void* mask, int mask_bits, const unsigned char* keep, const int* frame_of, const int* class_of,
+                  int P, int B, int N, int64_t set_stride, const Workspace& w, hipStream_t st) {
+    if (mask_bits == 64)
+        icp_select_kernel<int64_t><<<static_cast<unsigned>(P), kBlock, 0, st>>>(pcld, static_cast<const int64_t*>(mask), keep, frame_of, class_of,
+                                                                                 B, N, set_stride, w.sets, w.counts);
+    else
+        icp_select_kernel<int32_t><<<static_cast<unsigned>(P), kBlock, 0, st>>>(pcld, static_cast<const int32_t*>(mask), keep, frame_of, class_of,
+                                                                                 B, N, set_stride, w.sets, w.counts);
+    FFB6D_LAUNCH_CHECK();
+    return 0;
+}
+
+}  // namespace
+
+extern "C" {
+
+void ffb6d_icp_set_form(int form) { g_form = form < 0 ? -1 : (form ? 1 : 0); }
+
+int ffb6d_icp_set_pair_counter(unsigned long long* device_counter) {
+    g_pairs = device_counter;
+    return 0;
+}
+
+size_t ffb6d_icp_prepared_bytes(int64_t total, int n_cls) {
+    if (total < 0 || n_cls <= 0) return 0;
+    return prepared_layout(total, n_cls).bytes;
+}
+
+int ffb6d_icp_prepare(const float* model_pts, const int64_t* model_begin, int n_cls, int64_t total, void* prepared, size_t prepared_bytes,
+                      ffb6d_stream_t stream) {
+    FFB6D_REQUIRE(n_cls > 0 && total >= 0 && total < (int64_t(1) << 31), "icp_prepare: bad sizes n_cls=%d total=%lld", n_cls, (long long)total);
+    FFB6D_REQUIRE(model_begin && prepared && (total == 0 || model_pts), "icp_prepare: null pointer");
+    const Layout l = prepared_layout(total, n_cls);
+    if (prepared_bytes < l.bytes) return ffb6d::set_error(FFB6D_ERR_WORKSPACE, "icp_prepare: buffer %zu < %zu bytes", prepared_bytes, l.bytes);
+    hipStream_t st = ffb6d::as_stream(stream);
+    std::vector<int64_t> begin(static_cast<size_t>(n_cls) + 1);
+    std::vector<float> pts(static_cast<size_t>(total) * 3);
+    FFB6D_HIP_TRY(hipMemcpyAsync(begin.data(), model_begin, sizeof(int64_t) * begin.size(), hipMemcpyDeviceToHost, st));
+    if (total > 0) FFB6D_HIP_TRY(hipMemcpyAsync(pts.data(), model_pts, sizeof(float) * pts.size(), hipMemcpyDeviceToHost, st));
+    FFB6D_HIP_TRY(hipStreamSynchronize(st));
+    bool ok = begin[0] == 0 && begin[n_cls] == total;
+    for (int c = 0; c < n_cls && ok; ++c) ok = begin[c + 1] >= begin[c];
+    FFB6D_REQUIRE(ok, "icp_prepare: model_begin is not a rising table from 0 to total=%lld", (long long)total);
+
+    std::vector<unsigned char> blob(l.bytes, 0);
+    ClassInfo* cls = reinterpret_cast<ClassInfo*>(blob.data() + l.cls);
+    float4* cls_lo = reinterpret_cast<float4*>(blob.data() + l.cls_box);
+    float4* cls_hi = cls_lo + n_cls;
+    float4* orig = reinterpret_cast<float4*>(blob.data() + l.orig);
+    float4* sorted = reinterpret_cast<float4*>(blob.data() + l.sorted);
+    float4* tile_lo = reinterpret_cast<float4*>(blob.data() + l.tile_box);
+    float4* tile_hi = tile_lo + l.max_tiles;
+    const float inf = std::numeric_limits<float>::infinity(), qnan = std::numeric_limits<float>::quiet_NaN();
+    float no_index;
+    const int no_index_bits = kNoIndex;
+    std::memcpy(&no_index, &no_index_bits, sizeof(float));
+    for (int64_t i = 0; i < total; ++i) orig[i] = make_float4(pts[3 * i], pts[3 * i + 1], pts[3 * i + 2], 0.f);
+    int tile_begin = 0;
+    std::vector<unsigned long long> order;
+    for (int c = 0; c < n_cls; ++c) {
+        const int64_t b0 = begin[c];
+        const int n = static_cast<int>(begin[c + 1] - b0);
+        const int nt = (n + kTilePts - 1) / kTilePts;
+        cls[c] = ClassInfo{static_cast<int>(b0), n, tile_begin, nt};
+        float lo[3] = {inf, inf, inf}, hi[3] = {-inf, -inf, -inf};
+        for (int i = 0; i < n; ++i)
+            for (int k = 0; k < 3; ++k) {
+                const float v = pts[3 * (b0 + i) + k];
+                if (v < lo[k]) lo[k] = v;
+                if (v > hi[k]) hi[k] = v;
+            }
+        for (int k = 0; k < 3; ++k)
+            if (!(lo[k] <= hi[k])) lo[k] = hi[k] = 0.f;
+        cls_lo[c] = make_float4(lo[0], lo[1], lo[2], 0.f);
+        cls_hi[c] = make_float4(hi[0], hi[1], hi[2], 0.f);
+        order.resize(static_cast<size_t>(n));
+        for (int i = 0; i < n; ++i) {
+            unsigned q[3];
+            for (int k = 0; k < 3; ++k) {
+                const float ext = hi[k] - lo[k];
+                const float v = ext > 0.f ? (pts[3 * (b0 + i) + k] - lo[k]) / ext * 1023.f : 0.f;
+                q[k] = v >= 0.f ? (v < 1023.f ? static_cast<unsigned>(v) : 1023u) : 0u;      // (NaN: 0)
+            }
+            order[i] = (static_cast<unsigned long long>(morton10(q[0], q[1], q[2])) << 32) | static_cast<unsigned>(i);
+        }
+        std::sort(order.begin(), order.end());
+        for (int t = 0; t < nt; ++t) {
+            float tl[3] = {inf, inf, inf}, th[3] = {-inf, -inf, -inf};
+            for (int k = 0; k < kTilePts; ++k) {
+                const int j = t * kTilePts + k;
+                float4& dst = sorted[static_cast<int64_t>(tile_begin + t) * kTilePts + k];
+                if (j >= n) {
+                    dst = make_float4(qnan, qnan, qnan, no_index);
+                    continue;
+                }
+                const int i = static_cast<int>(order[j] & 0xffffffffull);
+                float idx_bits;
+                std::memcpy(&idx_bits, &i, sizeof(float));
+                const float* pt = &pts[3 * (b0 + i)];
+                dst = make_float4(pt[0], pt[1], pt[2], idx_bits);
+                for (int d = 0; d < 3; ++d) {
+                    if (pt[d] < tl[d]) tl[d] = pt[d];
+                    if (pt[d] > th[d]) th[d] = pt[d];
+                }
+            }
+            for (int d = 0; d < 3; ++d)
+                if (!(tl[d] <= th[d])) tl[d] = th[d] = 0.f;
+            tile_lo[tile_begin + t] = make_float4(tl[0], tl[1], tl[2], 0.f);
+            tile_hi[tile_begin + t] = make_float4(th[0], th[1], th[2], 0.f);
+        }
+        tile_begin += nt;
+    }
+    FFB6D_HIP_TRY(hipMemcpyAsync(prepared, blob.data(), l.bytes, hipMemcpyHostToDevice, st));
+    FFB6D_HIP_TRY(hipStreamSynchronize(st));
+    return 0;
+}
+
+size_t ffb6d_icp_workspace_bytes(int P, int64_t set_stride) {
+    if (P <= 0 || set_stride <= 0) return 0;
+    return workspace_layout(nullptr, P, set_stride).bytes;
+}
+
+int ffb6d_icp_correspond_f32(const void* prepared, int n_cls, int64_t total, const float* pcld, const void* mask, int mask_bits,
+                             const unsigned char* keep, const int* frame_of, const int* class_of, const double* T, int P, int B, int N,
+                             int64_t set_stride, float max_dist, int* idx, float* d2, int* counts, void* workspace, size_t workspace_bytes,
+                             ffb6d_stream_t stream) {
+    const int rc = check_scene_args("icp_correspond", prepared, n_cls, total, pcld, mask, mask_bits, frame_of, class_of, T, P, B, N, set_stride,
+                                    max_dist, workspace, workspace_bytes);
+    if (rc != 0 || P == 0) return rc;
+    hipStream_t st = ffb6d::as_stream(stream);
+    const Workspace w = workspace_layout(workspace, P, set_stride);
+    const int rs = launch_select(pcld, mask, mask_bits, keep, frame_of, class_of, P, B, N, set_stride, w, st);
+    if (rs != 0) return rs;
+    if (idx || d2) {
+        const int64_t n = static_cast<int64_t>(P) * set_stride;
+        icp_fill_kernel<<<static_cast<unsigned>(ceil_div(n, kBlock)), kBlock, 0, st>>>(idx, d2, n);
+        FFB6D_LAUNCH_CHECK();
+        CorrArgs a;
+        a.sets = w.sets; a.counts = w.counts; a.stride = set_stride; a.class_of = class_of; a.T = T; a.done = nullptr;
+        a.m = prepared_view(prepared, prepared_layout(total, n_cls), n_cls);
+        a.n_cls = n_cls; a.max_d2 = max_dist * max_dist; a.form = g_form; a.idx_out = idx; a.d2_out = d2; a.partials = nullptr;
+        a.tiles = w.tiles; a.pairs = g_pairs;
+        icp_correspond_kernel<<<dim3(static_cast<unsigned>(w.tiles), static_cast<unsigned>(P)), kBlock, 0, st>>>(a);
+        FFB6D_LAUNCH_CHECK();
+    }
+    if (counts) FFB6D_HIP_TRY(hipMemcpyAsync(counts, w.counts, sizeof(int) * P, hipMemcpyDeviceToDevice, st));
+    return 0;
+}
+
+int ffb6d_icp_refine_f32(const void* prepared, int n_cls, int64_t total, const float* pcld, const void* mask, int mask_bits,
+                         const unsigned char* keep, const int* frame_of, const int* class_of, const double* T0, int P, int B, int N,
+                         int64_t set_stride, float max_dist, int max_iter, double tol, int min_pairs, double* T, int* n_pairs, float* rms,
+                         int* iters, void* workspace, size_t workspace_bytes, ffb6d_stream_t stream) {
+    FFB6D_REQUIRE(max_iter >= 0 && tol >= 0.0 && min_pairs >= 1, "icp_refine: bad max_iter=%d / tol=%g / min_pairs=%d", max_iter, tol, min_pairs);
+    const int rc = check_scene_args("icp_refine", prepared, n_cls, total, pcld, mask, mask_bits, frame_of, class_of, T0, P, B, N, set_stride,
+                                    max_dist, workspace, workspace_bytes);
+    if (rc != 0 || P == 0) return rc;
+    hipStream_t st = ffb6d::as_stream(stream);
+    const Workspace w = workspace_layout(workspace, P, set_stride);
+    FFB6D_HIP_TRY(hipMemsetAsync(static_cast<char*>(workspace) + w.state_off, 0, w.state_bytes, st));
+    FFB6D_HIP_TRY(hipMemcpyAsync(w.T, T0, sizeof(double) * 12 * P, hipMemcpyDeviceToDevice, st));
+    if (max_iter > 0) {
+        const int rs = launch_select(pcld, mask, mask_bits, keep, frame_of, class_of, P, B, N, set_stride, w, st);
+        if (rs != 0) return rs;
+    }
+    CorrArgs a;
+    a.sets = w.sets; a.counts = w.counts; a.stride = set_stride; a.class_of = class_of; a.T = w.T; a.done = w.done;
+    a.m = prepared_view(prepared, prepared_layout(total, n_cls), n_cls);
+    a.n_cls = n_cls; a.max_d2 = max_dist * max_dist; a.form = g_form; a.idx_out = nullptr; a.d2_out = nullptr; a.partials = w.partials;
+    a.tiles = w.tiles; a.pairs = g_pairs;
+    SolveArgs s;
+    s.counts = w.counts; s.class_of = class_of; s.m = a.m; s.n_cls = n_cls; s.partials = w.partials; s.tiles = w.tiles; s.T = w.T;
+    s.done = w.done; s.iters = w.iters; s.n_pairs = w.n_pairs; s.rms = w.rms; s.min_pairs = min_pairs; s.tol = tol;
+    for (int it = 0; it < max_iter; ++it) {
+        icp_correspond_kernel<<<dim3(static_cast<unsigned>(w.tiles), static_cast<unsigned>(P)), kBlock, 0, st>>>(a);
+        FFB6D_LAUNCH_CHECK();
+        icp_solve_kernel<<<static_cast<unsigned>(P), 64, 0, st>>>(s);
+        FFB6D_LAUNCH_CHECK();
+    }
+    if (T) FFB6D_HIP_TRY(hipMemcpyAsync(T, w.T, sizeof(double) * 12 * P, hipMemcpyDeviceToDevice, st));
+    if (n_pairs) FFB6D_HIP_TRY(hipMemcpyAsync(n_pairs, w.n_pairs, sizeof(int) * P, hipMemcpyDeviceToDevice, st));
+    if (rms) FFB6D_HIP_TRY(hipMemcpyAsync(rms, w.rms, sizeof(float) * P, hipMemcpyDeviceToDevice, st));
+    if (iters) FFB6D_HIP_TRY(hipMemcpyAsync(iters, w.iters, sizeof(int) * P, hipMemcpyDeviceToDevice, st));
+    return 0;
+}
+
+}  // extern "C"

@@ -25,13 +25,16 @@ class SensorToPose:
     normals: "depth" = estimate them from the depth image (inputs.depth_normal: the LINE-MOD estimator behind the reference's
     normalSpeed call, linemod_dataset.py:252-254) or "given" = the sensor batch carries them.
     pose_inputs: optional callable (inp, out) -> (pcld [B,N,3], mask [B,N], ctr_of [B,1,N,3], kp_of [B,n_kps,N,3]) replacing the
-    network's own votes (benchmarks with random weights feed a synthetic 5-object vote field; the stage still waits for the forward)."""
+    network's own votes (benchmarks with random weights feed a synthetic 5-object vote field; the stage still waits for the forward).
+    refine: None, or the dict pose.solve_poses takes (models=refine.PreparedModels, max_iter, max_dist, ...): ICP refinement of the
+    fitted poses as the last step of stage C (on the pose side stream under the overlapped schedule)."""
 
     def __init__(self, net, K, n_points, mesh_kps, mesh_ctr, r_lst=None, classes=None, normals="depth", cam_scale=1.0,
-                 pose_inputs=None, seed=0):
+                 pose_inputs=None, seed=0, refine=None):
         self.net, self.K, self.n_points = net, np.asarray(K, np.float64), int(n_points)
         self.mesh_kps, self.mesh_ctr, self.r_lst, self.classes = mesh_kps, mesh_ctr, r_lst, classes
         self.normals, self.cam_scale, self.pose_inputs, self.seed = normals, float(cam_scale), pose_inputs, int(seed)
+        self.refine = refine
         self.dev = next(net.parameters()).device
         self._streams = None
 
@@ -61,7 +64,8 @@ class SensorToPose:
         else:
             pcld, mask = inp["cld"], out["pred_rgbd_segs"].argmax(dim=1)            # train_lm.py:385 / demo.py:160
             ctr_of, kp_of = out["pred_ctr_ofs"], out["pred_kp_ofs"]
-        return _pose.solve_poses(pcld, mask, ctr_of, kp_of, self.mesh_kps, self.mesh_ctr, r_lst=self.r_lst, classes=self.classes)
+        return _pose.solve_poses(pcld, mask, ctr_of, kp_of, self.mesh_kps, self.mesh_ctr, r_lst=self.r_lst, classes=self.classes,
+                                 refine=self.refine)
 
     # ---- schedules ------------------------------------------------------------------------------------------------
     def _side(self):

@@ -144,7 +144,7 @@ def best_fit_transform(A, B, device=None):
 
 
 def solve_poses(pcld, mask, ctr_of, kp_of, mesh_kps, mesh_ctr, r_lst=None, use_ctr=True,
-                use_ctr_clus_flter=True, refine_mask=None, classes=None, radius=RADIUS, max_iter=300, stats=None):
+                use_ctr_clus_flter=True, refine_mask=None, classes=None, radius=RADIUS, max_iter=300, stats=None, refine=None):
     """All objects of all frames at once.
       pcld f32 [B,N,3]; mask int [B,N] predicted class per point (0 = background);
       ctr_of f32 [B,1,N,3], kp_of f32 [B,n_kps,N,3] (end_points['pred_ctr_ofs'/'pred_kp_ofs']);
@@ -154,6 +154,10 @@ def solve_poses(pcld, mask, ctr_of, kp_of, mesh_kps, mesh_ctr, r_lst=None, use_c
                solved in every frame whether present or not (LineMOD flow: [1], :238-241);
       refine_mask: centre-clustering mask filter (:83-108); default = use_ctr_clus_flter and classes is None.
       stats: optional dict, receives the rounds made per set of each mean-shift pass.
+      refine: None, or dict(models=refine.PreparedModels, max_iter=..., max_dist=..., [tol, min_pairs]): the fitted poses of every
+              (frame, object) pair go through ONE refine.icp_refine call (ICP against the points of `pcld` that the `mask` given
+              here assigns to the object) before they are read back; the keypoints column stays as fitted ("refine" in stats
+              receives the call's n_pairs / rms / iters).
     Returns a list over frames of (class_ids int array, poses [n,3,4] float64, kps [n,n_kps+1,3] float32);
     objects without points get the identity pose and zero keypoints (:114-117 / :239-240)."""
     _need_gpu(pcld, mask, ctr_of, kp_of)
@@ -166,6 +170,7 @@ def solve_poses(pcld, mask, ctr_of, kp_of, mesh_kps, mesh_ctr, r_lst=None, use_c
     if refine_mask is None:
         refine_mask = use_ctr_clus_flter and classes is None
     mask = mask.contiguous()
+    mask_given = mask
     lib = _lib.load()
 
     if classes is None:
@@ -229,6 +234,12 @@ def solve_poses(pcld, mask, ctr_of, kp_of, mesh_kps, mesh_ctr, r_lst=None, use_c
         T = best_fit_transform_batch(model, found)
     else:
         T = best_fit_transform_batch(model[:, :n_kps], found[:, :n_kps])
+    if refine is not None:
+        from . import refine as _refine
+        opts = dict(refine)
+        T, rstats = _refine.icp_refine(pcld, mask_given, T, frame_of, class_of, opts.pop("models"), **opts)
+        if stats is not None:
+            stats["refine"] = rstats
 
     empty = (counts == 0).cpu().numpy()
     T = T.cpu().numpy()

@@ -1,0 +1,134 @@
+"""ICP pose refinement on the GPU: the step after the keypoint fit (pose.solve_poses), the second column of every published
+FFB6D / PVN3D table.  Host side of include/ffb6d_refine.h, which states the algorithm (point-to-point, scene -> model, every
+(frame, object) pair of a batch in the same launches); the reference repository has no counterpart -- tests/icp_ref.py is the
+numpy restatement the kernels are held against.
+
+    models = refine.PreparedModels(evaluate.ModelPoints(clouds))          # once per model set
+    poses, stats = refine.icp_refine(pcld, mask, poses, frame_of, class_of, models, max_iter=10, max_dist=0.02)
+
+`icp_refine` and `correspondences` enqueue their kernels on the current stream and return device tensors: nothing is read
+back and the stream is never waited for.  There is no CPU fallback: tensors must live on a GPU.
+"""
+import numpy as np
+import torch
+
+from . import _lib
+from .ops import _need_gpu, _stream
+from .pose import _mask_bits
+
+FORM = 0               # csrc/icp.hip ffb6d_icp_set_form: 0 = scan (default), 1 = pruned, -1 = pruned from 1024 model points on
+
+
+def set_form(form):
+    """0 scan (default) / 1 pruned / -1 automatic; returns the previous setting.  Results do not depend on it."""
+    global FORM
+    prev, FORM = FORM, int(form)
+    _lib.load().ffb6d_icp_set_form(FORM)
+    return prev
+
+
+class PreparedModels:
+    """The model clouds of an evaluate.ModelPoints prepared for the search (Morton order, 64-point tiles with their boxes),
+    once per model set.  Preparing copies the clouds to the host and back: it waits for the device."""
+
+    def __init__(self, models):
+        _need_gpu(models.pts, models.begin)
+        self.models, self.device = models, models.device
+        self.n_cls, self.counts = int(models.n_cls), np.asarray(models.counts, np.int64)
+        self.total = int(self.counts.sum())
+        lib = _lib.load()
+        nbytes = lib.ffb6d_icp_prepared_bytes(self.total, self.n_cls)
+        self.buf = torch.empty((max(nbytes, 1),), dtype=torch.uint8, device=self.device)
+        with torch.cuda.device(self.device):
+            rc = lib.ffb6d_icp_prepare(models.pts.data_ptr() if self.total else None, models.begin.data_ptr(), self.n_cls, self.total,
+                                       self.buf.data_ptr(), nbytes, _stream(self.buf))
+        _lib.check(rc, "ffb6d_icp_prepare")
+
+
+def _prepared(models):
+    return models if isinstance(models, PreparedModels) else PreparedModels(models)
+
+
+def _problems(pcld, mask, poses, frame_of, class_of, models, keep):
+    """Validates what the host can see and brings every argument into the layout of the C ABI."""
+    _need_gpu(pcld, mask)
+    for t in (poses, frame_of, class_of, keep):
+        if torch.is_tensor(t):
+            _need_gpu(t)
+    if pcld.dim() != 3 or pcld.shape[2] != 3 or mask.shape != pcld.shape[:2]:
+        raise ValueError(f"expected pcld [B,N,3] and mask [B,N], got {tuple(pcld.shape)} / {tuple(mask.shape)}")
+    dev = pcld.device
+    if models.device != dev:
+        raise ValueError(f"models live on {models.device}, the cloud on {dev}")
+    B = pcld.shape[0]
+    for name, ids, hi in (("frame_of", frame_of, B), ("class_of", class_of, models.n_cls)):
+        if not torch.is_tensor(ids):                            # host-visible ids are checked here; device ids that are no index
+            a = np.asarray(ids).reshape(-1)                     # give a problem without pairs (include/ffb6d_refine.h)
+            if len(a) and (a.min() < 0 or a.max() >= hi):
+                raise ValueError(f"{name} outside [0, {hi})")
+    as_i32 = lambda x: (x if torch.is_tensor(x) else torch.as_tensor(np.asarray(x, np.int32).reshape(-1))).to(       # noqa: E731
+        device=dev, dtype=torch.int32).reshape(-1).contiguous()
+    frame_of, class_of = as_i32(frame_of), as_i32(class_of)
+    P = int(frame_of.shape[0])
+    poses = poses if torch.is_tensor(poses) else torch.as_tensor(np.asarray(poses, np.float64))
+    poses = poses.to(device=dev, dtype=torch.float64).reshape(-1, 3, 4).contiguous()
+    if int(class_of.shape[0]) != P or int(poses.shape[0]) != P:
+        raise ValueError(f"{P} frames / {int(class_of.shape[0])} classes / {int(poses.shape[0])} poses")
+    if keep is not None:
+        if keep.shape != mask.shape:
+            raise ValueError(f"keep {tuple(keep.shape)} does not match mask {tuple(mask.shape)}")
+        keep = keep.to(torch.uint8).contiguous()
+    return pcld.contiguous().float(), mask.contiguous(), poses, frame_of, class_of, keep, P
+
+
+def correspondences(pcld, mask, poses, frame_of, class_of, models, max_dist=float("inf"), keep=None):
+    """One evaluation of steps 1-3: for the j-th scene point of problem p (the points of pcld[frame_of[p]] with
+    mask == class_of[p], and keep != 0 when given, in index order) under poses[p] (f64 [P,3,4], model -> camera)
+    -> idx i32 [P,N] (model point within the class; -1 where the pair is gated out or j is beyond the count),
+       d2 f32 [P,N] (squared distance to it, kept or not; +inf beyond the count), counts i32 [P]."""
+    models = _prepared(models)
+    pcld, mask, poses, frame_of, class_of, keep, P = _problems(pcld, mask, poses, frame_of, class_of, models, keep)
+    B, N, _ = pcld.shape
+    dev = pcld.device
+    idx = torch.empty((P, N), dtype=torch.int32, device=dev)
+    d2 = torch.empty((P, N), dtype=torch.float32, device=dev)
+    counts = torch.empty((P,), dtype=torch.int32, device=dev)
+    lib = _lib.load()
+    wbytes = lib.ffb6d_icp_workspace_bytes(P, N)
+    ws = torch.empty((max(wbytes, 1),), dtype=torch.uint8, device=dev)
+    with torch.cuda.device(dev), _lib.traced("icp_correspond", 0, (P, N)):
+        rc = lib.ffb6d_icp_correspond_f32(models.buf.data_ptr(), models.n_cls, models.total, pcld.data_ptr(), mask.data_ptr(),
+                                          _mask_bits(mask), keep.data_ptr() if keep is not None else None, frame_of.data_ptr(),
+                                          class_of.data_ptr(), poses.data_ptr(), P, B, N, N, float(max_dist), idx.data_ptr(),
+                                          d2.data_ptr(), counts.data_ptr(), ws.data_ptr(), wbytes, _stream(pcld))
+    _lib.check(rc, "ffb6d_icp_correspond_f32")
+    return idx, d2, counts
+
+
+def icp_refine(pcld, mask, poses, frame_of, class_of, models, max_iter=10, max_dist=0.02, tol=0.0, min_pairs=3, keep=None):
+    """The whole loop for P problems: pcld f32 [B,N,3], mask int32|int64 [B,N], poses [P,3,4] (model -> camera), frame_of /
+    class_of [P], models a PreparedModels (or an evaluate.ModelPoints, prepared on the spot: that waits for the device).
+      max_dist: gate in metres (inf keeps every pair); tol: early stop when an update moves no corner of the model's bounding
+      box by more than this many metres (0 = always max_iter iterations); min_pairs: fewer kept pairs end the problem with
+      the pose it has.
+    -> (poses f64 [P,3,4], dict n_pairs i32 [P], rms f32 [P] (of the last iteration made, before its update), iters i32 [P]),
+    all on the device."""
+    models = _prepared(models)
+    pcld, mask, poses, frame_of, class_of, keep, P = _problems(pcld, mask, poses, frame_of, class_of, models, keep)
+    B, N, _ = pcld.shape
+    dev = pcld.device
+    T = torch.empty((P, 3, 4), dtype=torch.float64, device=dev)
+    n_pairs = torch.empty((P,), dtype=torch.int32, device=dev)
+    rms = torch.empty((P,), dtype=torch.float32, device=dev)
+    iters = torch.empty((P,), dtype=torch.int32, device=dev)
+    lib = _lib.load()
+    wbytes = lib.ffb6d_icp_workspace_bytes(P, N)
+    ws = torch.empty((max(wbytes, 1),), dtype=torch.uint8, device=dev)
+    with torch.cuda.device(dev), _lib.traced("icp_refine", 0, (P, N, int(max_iter))):
+        rc = lib.ffb6d_icp_refine_f32(models.buf.data_ptr(), models.n_cls, models.total, pcld.data_ptr(), mask.data_ptr(),
+                                      _mask_bits(mask), keep.data_ptr() if keep is not None else None, frame_of.data_ptr(),
+                                      class_of.data_ptr(), poses.data_ptr(), P, B, N, N, float(max_dist), int(max_iter), float(tol),
+                                      int(min_pairs), T.data_ptr(), n_pairs.data_ptr(), rms.data_ptr(), iters.data_ptr(),
+                                      ws.data_ptr(), wbytes, _stream(pcld))
+    _lib.check(rc, "ffb6d_icp_refine_f32")
+    return T, dict(n_pairs=n_pairs, rms=rms, iters=iters)
