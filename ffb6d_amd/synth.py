@@ -315,3 +315,36 @@ def pose_case_ground_truth(case, extra_seed=None):
         kps += [kps[0] + 0.05, np.zeros_like(kps[0]), kps[0]]
     return (np.asarray(ids, np.int64).reshape(-1, 1), np.asarray(RTs).astype(np.float32),
             np.asarray(kps).astype(np.float32))
+
+
+# ---- rendering: vertex-coloured triangle meshes ----------------------------------------------------------------
+def sphere_mesh(subdiv, radius=0.1, seed=0):
+    """An icosphere as a vertex-coloured triangle mesh: dict(xyz f32 [V,3] on the sphere of `radius` metres, rgb u8 [V,3]
+    seeded colours, faces i32 [F,3] wound counter-clockwise seen from outside), F = 20 * 4^subdiv, V = 10 * 4^subdiv + 2.
+    Every subdivision cuts each triangle into four at its edge midpoints, pushed out to the sphere."""
+    g = (1.0 + np.sqrt(5.0)) / 2.0
+    verts = [(-1, g, 0), (1, g, 0), (-1, -g, 0), (1, -g, 0), (0, -1, g), (0, 1, g), (0, -1, -g), (0, 1, -g),
+             (g, 0, -1), (g, 0, 1), (-g, 0, -1), (-g, 0, 1)]
+    verts = [np.asarray(v, np.float64) / np.sqrt(1.0 + g * g) for v in verts]
+    faces = [(0, 11, 5), (0, 5, 1), (0, 1, 7), (0, 7, 10), (0, 10, 11), (1, 5, 9), (5, 11, 4), (11, 10, 2), (10, 7, 6),
+             (7, 1, 8), (3, 9, 4), (3, 4, 2), (3, 2, 6), (3, 6, 8), (3, 8, 9), (4, 9, 5), (2, 4, 11), (6, 2, 10), (8, 6, 7),
+             (9, 8, 1)]
+    for _ in range(int(subdiv)):
+        mid = {}
+
+        def midpoint(a, b):
+            key = (a, b) if a < b else (b, a)
+            if key not in mid:
+                m = verts[a] + verts[b]
+                verts.append(m / np.linalg.norm(m))
+                mid[key] = len(verts) - 1
+            return mid[key]
+
+        nxt = []
+        for a, b, c in faces:
+            ab, bc, ca = midpoint(a, b), midpoint(b, c), midpoint(c, a)
+            nxt += [(a, ab, ca), (b, bc, ab), (c, ca, bc), (ab, bc, ca)]
+        faces = nxt
+    rng = np.random.RandomState(seed)
+    xyz = (np.asarray(verts) * float(radius)).astype(np.float32)
+    return dict(xyz=xyz, rgb=rng.randint(0, 256, (len(xyz), 3)).astype(np.uint8), faces=np.asarray(faces, np.int32))

@@ -462,3 +462,20 @@ def assemble_training_batch(rgb, depth, label_img, K, n_points, cls_ids, RTs, me
     out.update(tg)
     out["rgb_labels"] = label_img.to(torch.int32)
     return out
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# synthetic frames from meshes and poses
+# ---------------------------------------------------------------------------------------------------------------------
+def render_synthetic(meshes, poses, frame_of, class_of, K, B, H, W, depth_scale=1.0, min_visible=0):
+    """The synthetic frames the reference reads from renders/ ("render": one instance per frame) and fuse/ ("fuse": several,
+    occluding one another; linemod_dataset.py:209-249), drawn on the device from meshes and poses (ffb6d_amd/render.py):
+      meshes: a render.PreparedMeshes (or its list); poses [I,3,4] (model -> camera, metres), frame_of / class_of [I], K.
+    Returns (rgb uint8 [B,3,H,W], depth float32 [B,H,W] = metres * depth_scale (the raw units of a sensor whose cam_scale is
+    depth_scale), label int32 [B,H,W] (class id, 0 = background), ok bool [I] = the instance owns at least min_visible pixels;
+    the reference discards renders below 500, rgbd_rnder_sift_kp3ds.py:80): the rgb / depth / label_img that
+    assemble_training_batch(..., synthetic=...) takes."""
+    from . import render as _render
+    out = _render.render(meshes, poses, frame_of, class_of, K, B, H, W, outputs=("rgb", "depth", "label", "visible"))
+    depth = out["depth"] if depth_scale == 1.0 else out["depth"] * float(depth_scale)
+    return out["rgb"], depth, out["label"], out["visible"] >= int(min_visible)
