@@ -1,6 +1,6 @@
 // ffb6d_amd/csrc/seg_sort.h -- stable segmented radix sort of (32-bit key, 32-bit value) pairs, hand-written for gfx950 (csrc/seg_sort.hip).
-// Used by the exact-KNN set preparation (Morton order of up to 8 point sets x B frames in ONE sort, csrc/knn_pruned.hip) and by the pose
-// solver's duplicate merging (csrc/pose.hip).  Replaces rocprim::radix_sort_pairs on the hot path: for the ~1 M keys of an index
+// Used by the exact-KNN set preparation (Morton order of up to 8 point sets x B frames in ONE sort, csrc/knn_pruned.hip) and by the
+// input pipeline's valid-pixel sampling (the frames are the segments, csrc/inputs.hip).  Replaces rocprim::radix_sort_pairs on the hot path: for the ~1 M keys of an index
 // pyramid rocPRIM ran its merge sort, 20 dependent launches = 0.13 ms alone and 0.40 ms inside the three-stream bench step
 // (profiles/r04_rocprofv3_kernel_stats_steady_state.txt); this sort is 2 launches per 8-bit digit.
 #pragma once

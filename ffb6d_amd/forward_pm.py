@@ -218,6 +218,36 @@ def decode(stage, skip, p_emb, interp_idx):
 
 
 # ----------------------------------------------------------------------------------------------------
+# fusion
+# ----------------------------------------------------------------------------------------------------
+def fusion_step(pre_p2r, fuse_p2r, pre_r2p, fuse_r2p, rgb0, p0, p2r_idx, r2p_idx, main=None, side=None, handover=None, tag=""):
+    """One bidirectional fusion step (ffb6d.py:245-263 / 281-298) on the four SharedMLPs of one stage; both directions read the
+    pre-fusion tensors: rgb0 [B,h,w,c] (produced on `main`), p0 [B,n,cp] (produced on `side`), p2r_idx [B,h*w,1] (pixel -> nearest
+    point), r2p_idx [B,n,16] (point -> nearest pixels) -> (rgb [B,h,w,c] on `main`, p [B,n,cp] on `side`).
+    `forward` passes its two streams and its `handover(tensor, producer, consumer, tag)`; a caller with one stream (stage-level
+    tests) leaves them out and everything runs on the current stream.  Each output row depends on its own input rows only, so the
+    pixel side may be any subset of pixel rows laid out as [B,1,rows,c] with the indices renumbered to match."""
+    B, h, w_, c = rgb0.shape
+    if main is None:
+        main = side = torch.cuda.current_stream(rgb0.device)
+    if handover is None:
+        handover = lambda t, producer, consumer, tag=None: t                        # noqa: E731
+    handover(p0, side, main, "main waits for point stage " + tag)
+    handover(rgb0, main, side, "side waits for colour stage " + tag)
+    if side is not main:
+        p2r_idx.record_stream(main)
+    # p2r on main: conv(cat(rgb0, interp(e))) = W_a rgb0 + gather(W_b e)
+    e = mlp(pre_p2r, p0)
+    wa, wb, bias = split(fuse_p2r, c, rgb0.dtype)
+    y = ops_pm.mlp(e, wb)
+    rgb = ops_pm.mlp(rgb0, wa, bias, fuse_p2r.act_code, gather=(y, p2r_idx.reshape(B, -1)))
+    with torch.cuda.stream(side):     # r2p: max over the 16 nearest pixels, then conv(cat(p0, pre(.))) as a two-source GEMM
+        r2p = mlp(pre_r2p, ops_pm.random_sample(rgb0.view(B, h * w_, c), r2p_idx))
+        p = mlp(fuse_r2p, p0, x2=r2p)
+    return rgb, p
+
+
+# ----------------------------------------------------------------------------------------------------
 # colour branch (tensors kept as [B,H,W,C]; MIOpen sees them as channels_last NCHW views)
 # ----------------------------------------------------------------------------------------------------
 def conv(x, c):
@@ -532,22 +562,8 @@ def forward(net, inputs, end_points, two_streams=True, taps=None):
         return t
 
     def fuse(i, pre_p2r, fuse_p2r, pre_r2p, fuse_r2p, rgb0, p0, p2r_idx, r2p_idx):
-        """One bidirectional fusion step (ffb6d.py:245-263 / 281-298); both directions read the pre-fusion tensors."""
-        B, h, w_, c = rgb0.shape
         st = ("ds%d" if pre_p2r is net.ds_fuse_p2r_pre_layers else "up%d") % i
-        handover(p0, side, main, "main waits for point stage " + st)
-        handover(rgb0, main, side, "side waits for colour stage " + st)
-        if two_streams:
-            p2r_idx.record_stream(main)
-        # p2r on main: conv(cat(rgb0, interp(e))) = W_a rgb0 + gather(W_b e)
-        e = mlp(pre_p2r[i], p0)
-        wa, wb, bias = split(fuse_p2r[i], c, dt)
-        y = ops_pm.mlp(e, wb)
-        rgb = ops_pm.mlp(rgb0, wa, bias, fuse_p2r[i].act_code, gather=(y, p2r_idx.reshape(B, -1)))
-        with on_side():     # r2p: max over the 16 nearest pixels, then conv(cat(p0, pre(.))) as a two-source GEMM
-            r2p = mlp(pre_r2p[i], ops_pm.random_sample(rgb0.view(B, h * w_, c), r2p_idx))
-            p = mlp(fuse_r2p[i], p0, x2=r2p)
-        return rgb, p
+        return fusion_step(pre_p2r[i], fuse_p2r[i], pre_r2p[i], fuse_r2p[i], rgb0, p0, p2r_idx, r2p_idx, main, side, handover, st)
 
     # ---- stems ----
     rgb = inputs['rgb'].to(dt).contiguous(memory_format=torch.channels_last).permute(0, 2, 3, 1)   # [B,H,W,3] view

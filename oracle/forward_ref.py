@@ -9,7 +9,8 @@ Functional, plain-PyTorch fp32 CPU restatement of the reference's whole forward 
 driven directly by a reference-format state dict (no nn.Module tree), eval-mode semantics
 (BatchNorm uses running statistics, dropout is the identity).  It exists to check the HIP
 product path and to time the CPU baseline on hosts where /root/reference is absent; it is
-pinned to the reference by tests/golden/forward_small.npz (tests/test_oracle_cpu.py).
+pinned to the reference by tests/golden/forward_small.npz at the end points and by
+tests/golden/stage_taps_sample.npz at every stage boundary (tests/test_oracle_cpu.py).
 """
 import torch
 import torch.nn.functional as F
@@ -123,10 +124,13 @@ def head(x, w):
     return mlp_pvn(x, w.sub("3"), act=False)
 
 
-def ffb6d_forward(state_dict, inputs, n_kps=8, taps=None):
+def ffb6d_forward(state_dict, inputs, n_kps=8, taps=None, internals=False):
     """inputs: the reference's input dict (torch CPU tensors, int64 indices).
     taps: optional dict that receives the two embeddings after every fusion stage (`rgb_emb_ds{i}`, `p_emb_ds{i}`,
-    `rgb_emb_up{i}`, `p_emb_up{i}`, reference layout [B,C,H,W] / [B,C,N,1]) for stage-level parity checks."""
+    `rgb_emb_up{i}`, `p_emb_up{i}`, reference layout [B,C,H,W] / [B,C,N,1]) for stage-level parity checks.
+    internals: `taps` also receives the stage outputs between them -- `f_encoder_{i}` / `f_decoder_{i}` (rndla_ds_stages /
+    rndla_up_stages, i = 0..3) and `rgb_emb0_ds{i}` / `rgb_emb0_up{i}` (cnn_ds_stages / cnn_up_stages, i = 0..3).  All of these are
+    pinned to the reference's own tensors by tests/golden/stage_taps_sample.npz (tests/test_oracle_cpu.py)."""
     w = _W(state_dict)
     rgb_emb = F.conv2d(inputs["rgb"], w["cnn_pre_stages.0.weight"], None, 2, 3)
     rgb_emb = F.relu(_bn(rgb_emb, w.sub("cnn_pre_stages.1"), 1e-5))
@@ -150,6 +154,8 @@ def ffb6d_forward(state_dict, inputs, n_kps=8, taps=None):
         p_emb0 = ops_ref.random_sample(f_enc, inputs[f"cld_sub_idx{i}"])
         if i == 0:
             ds_emb.append(f_enc)
+        if taps is not None and internals:
+            taps[f"rgb_emb0_ds{i}"], taps[f"f_encoder_{i}"] = rgb_emb0, f_enc
         p2r = mlp_pvn(p_emb0, w.sub(f"ds_fuse_p2r_pre_layers.{i}"))
         p2r = ops_ref.nearest_interpolation(p2r, inputs[f"p2r_ds_nei_idx{i}"]).view(bs, -1, hr, wr)
         rgb_emb = mlp_pvn(torch.cat((rgb_emb0, p2r), dim=1), w.sub(f"ds_fuse_p2r_fuse_layers.{i}"))
@@ -166,6 +172,8 @@ def ffb6d_forward(state_dict, inputs, n_kps=8, taps=None):
         bs, c, hr, wr = rgb_emb0.shape
         f_interp = ops_ref.nearest_interpolation(p_emb, inputs[f"cld_interp_idx{3 - i}"])
         p_emb0 = mlp_randla(torch.cat([ds_emb[-i - 2], f_interp], dim=1), w.sub(f"rndla_up_stages.{i}"))
+        if taps is not None and internals:
+            taps[f"rgb_emb0_up{i}"], taps[f"f_decoder_{i}"] = rgb_emb0, p_emb0
         p2r = mlp_pvn(p_emb0, w.sub(f"up_fuse_p2r_pre_layers.{i}"))
         p2r = ops_ref.nearest_interpolation(p2r, inputs[f"p2r_up_nei_idx{i}"]).view(bs, -1, hr, wr)
         rgb_emb = mlp_pvn(torch.cat((rgb_emb0, p2r), dim=1), w.sub(f"up_fuse_p2r_fuse_layers.{i}"))
@@ -179,6 +187,8 @@ def ffb6d_forward(state_dict, inputs, n_kps=8, taps=None):
     rgb_emb = final_head(psp_upsample(rgb_emb, cw.sub("0")), cw.sub("1"))
     f_interp = ops_ref.nearest_interpolation(p_emb, inputs["cld_interp_idx0"])
     p_emb = mlp_randla(torch.cat([ds_emb[0], f_interp], dim=1), w.sub("rndla_up_stages.3")).squeeze(-1)
+    if taps is not None and internals:
+        taps["rgb_emb0_up3"], taps["f_decoder_3"] = rgb_emb, p_emb.unsqueeze(3)
     bs, di = rgb_emb.shape[:2]
     rgb_c = ops_ref.nearest_interpolation(rgb_emb.view(bs, di, -1, 1), inputs["choose"].view(bs, -1, 1)).squeeze(3)
     rgbd = torch.cat([rgb_c, p_emb], dim=1)

@@ -14,6 +14,11 @@ section 4 / 8c), so these files are what pins parity:
   state_dict_keys.json       parameter/buffer names and shapes of the reference FFB6D
   forward_small.npz          end_points of the reference FFB6D.forward on a small frame
   forward_full_sample.npz    strided samples of end_points at 480x640, N=12288
+
+Written by make_golden_taps.py (same small frame, weights and pyramid as forward_small.npz; forward hooks on the reference's modules):
+  stage_taps_sample.npz      strided samples of the reference's tensors at every stage boundary of its forward
+  stage_point_io.npz         inputs / outputs of its point encoder blocks, sub-sampling and decoder steps, whole
+  stage_fusion_io.npz        inputs / outputs of both fusion directions of encoder stage 1 and decoder stage 1
 """
 import hashlib
 import json

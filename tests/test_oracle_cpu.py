@@ -1,6 +1,7 @@
 """CPU suite: the oracle (our restatement of the reference algorithm) against the golden
 vectors produced by the reference itself (its compiled kd-tree, its operators and its back-projection included:
 tests/golden/make_golden_refcheck.py)."""
+import functools
 import hashlib
 import importlib.util
 import json
@@ -166,7 +167,10 @@ def test_depth_normal_restatement_recovers_plane_normals():
 
 
 # ---- whole-forward restatement (oracle/forward_ref.py) against the reference's end_points ----
+@functools.lru_cache(maxsize=None)
 def _oracle_forward(config, bs, n_points, h, w, n_classes):
+    """(end_points, taps with the internal stage outputs) of oracle/forward_ref.py on a synthetic batch whose index pyramid is
+    rebuilt with oracle.knn; computed once per geometry and shared (read only) by the tests below."""
     from oracle import forward_ref
     with open(os.path.join(GOLDEN, "state_dict_keys.json")) as fh:
         shapes = json.load(fh)
@@ -178,19 +182,87 @@ def _oracle_forward(config, bs, n_points, h, w, n_classes):
               "choose": torch.from_numpy(frames["choose"].astype(np.int64))}
     for k, v in pyr.items():
         inputs[k] = torch.from_numpy(v.astype(np.int64) if v.dtype == np.int32 else v)
+    taps = {}
     with torch.no_grad():
-        return forward_ref.ffb6d_forward(sd, inputs)
+        return forward_ref.ffb6d_forward(sd, inputs, taps=taps, internals=True), taps
 
 
 def test_oracle_forward_matches_reference_small_golden():
     """2 frames of 120x160, N=1024, 5 classes: full end_points of the reference FFB6D."""
     gold = np.load(os.path.join(GOLDEN, "forward_small.npz"))
-    ep = _oracle_forward(7, 2, 1024, 120, 160, 5)
+    ep, _ = _oracle_forward(7, 2, 1024, 120, 160, 5)
     for k in ("pred_rgbd_segs", "pred_kp_ofs", "pred_ctr_ofs"):
         assert ep[k].shape == gold[k].shape
         scale = float(np.abs(gold[k]).max())
         err = float(np.abs(ep[k].numpy() - gold[k]).max())
         assert err <= 1e-5 * max(scale, 1.0), (k, err, scale)
+
+
+# ---- the restatement's stage tensors against what forward hooks on the unmodified reference recorded (make_golden_taps.py) ----
+TAP_NAMES = ["%s_emb_%s" % (b, s) for s in ["ds%d" % i for i in range(4)] + ["up%d" % i for i in range(3)] for b in ("rgb", "p")]
+INTERNAL_NAMES = ["%s%d" % (n, i) for n in ("f_encoder_", "f_decoder_", "rgb_emb0_ds", "rgb_emb0_up") for i in range(4)]
+# Bar = 4 x the largest error measured over all 30 tensors (max |ours - reference| over the reference tensor's range, frame 0 of
+# the batch of 2), rounded up to one significant digit.  The factor covers oneDNN's choice of convolution algorithm per batch size
+# and thread count on another machine (end points move by ~1e-4 absolute between such runs); it is capped at the 1e-5 hot-path bar.
+# Measured: 1.148e-6 (f_decoder_2) -> 4 x = 4.6e-6 -> 5e-6.  (The same run restricted to one thread measures 1.53e-6: what the factor is for.)
+STAGE_PIN_BAR = 5e-6
+
+
+def _stage_pin(names):
+    z = np.load(os.path.join(GOLDEN, "stage_taps_sample.npz"))
+    _, taps = _oracle_forward(7, 2, 1024, 120, 160, 5)
+    assert sorted(k for k in z.files if "/" not in k) == sorted(TAP_NAMES + INTERNAL_NAMES) == sorted(taps)
+    worst = 0.0
+    for k in names:
+        full = taps[k][0].numpy()
+        got, want, scale = full.reshape(-1)[::int(z[k + "/stride"])], z[k], float(z[k + "/absmax"])
+        assert got.shape == want.shape and want.size >= min(full.size, 1000) and scale > 0, (k, got.shape, want.shape)
+        err = float(np.abs(got.astype(np.float64) - want).max()) / scale
+        worst = max(worst, err)
+        print("%-14s %-16s max err / range %.3e" % (k, tuple(full.shape), err))
+        assert err <= STAGE_PIN_BAR, (k, err)
+        assert abs(float(np.abs(full).max()) - scale) <= STAGE_PIN_BAR * scale, k
+    print("largest:", worst)
+
+
+def test_oracle_taps_match_the_hooked_reference():
+    """The 14 post-fusion embeddings `forward_ref.ffb6d_forward(taps=)` hands out -- the reference side of the GPU stage parity test
+    (tests/test_forward_gpu.py) -- against strided samples of the tensors the reference itself produced at the same boundaries
+    (ffb6d.py:251,260,287,296), by name: a mislabelled or misplaced tap fails here.
+    Measured on the build machine: 1.3e-7 (p_emb_ds0) .. 9.72e-7 (p_emb_up1) of each tensor's range, growing with depth; the colour side's
+    largest is rgb_emb_up0 8.7e-7."""
+    _stage_pin(TAP_NAMES)
+
+
+def test_oracle_internal_stages_match_the_hooked_reference():
+    """The stage outputs between the taps (`internals=True`): the point encoder / decoder blocks (rndla_ds_stages, rndla_up_stages)
+    and the colour stages (cnn_ds_stages, cnn_up_stages), against the hooked reference.
+    Measured on the build machine: 0 (rgb_emb0_ds0: three residual blocks, equal bits) .. 1.148e-6 (f_decoder_2), the largest of all 30
+    tensors; f_encoder_0..3 1.1e-7 .. 7.5e-7, the colour stages <= 7.9e-7."""
+    _stage_pin(INTERNAL_NAMES)
+
+
+@pytest.mark.reference
+def test_stage_fixtures_are_what_the_reference_computes_today():
+    """Staleness guard (build machine): the hooked reference run again in memory against the three committed stage fixtures -- same
+    keys, shapes and dtypes, index arrays equal, float arrays within STAGE_PIN_BAR of the committed tensor's range (equal bits on the
+    machine and thread count that wrote them; oneDNN's summation order moves with the thread count, measured <= 1.5e-6)."""
+    spec_t = importlib.util.spec_from_file_location("make_golden_taps", os.path.join(GOLDEN, "make_golden_taps.py"))
+    gen = importlib.util.module_from_spec(spec_t)
+    spec_t.loader.exec_module(gen)
+    for name, arrays in gen.generate(verbose=False).items():
+        z = np.load(os.path.join(GOLDEN, name))
+        assert sorted(z.files) == sorted(arrays), name
+        for k, v in arrays.items():
+            want = z[k]
+            assert want.dtype == v.dtype and want.shape == v.shape, (name, k)
+            if v.dtype == np.int32 or np.array_equal(want, v):
+                assert np.array_equal(want, v), (name, k)
+                continue
+            scale = float(z[k.split("/")[0] + "/absmax"]) if name == "stage_taps_sample.npz" else float(np.abs(want).max())
+            err = float(np.abs(v.astype(np.float64) - want).max()) / scale
+            print(name, k, "max err / range", err)
+            assert err <= STAGE_PIN_BAR, (name, k, err)
 
 
 def test_depth_backprojection_restatement_matches_the_frame_generator():
