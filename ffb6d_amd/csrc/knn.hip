@@ -15,17 +15,16 @@
 //     (exec-masked ds_write_b64), and the wave drains all queues together when any lane's
 //     queue is nearly full -- so the ~100-op insert runs with most lanes active instead
 //     of once per candidate with one lane active;
-//   * when B*ceil(Q/256) blocks cannot fill 256 CUs the support range is split across
-//     blockIdx.y and the per-split sorted lists are merged by a second tiny kernel
-//     (splits are merged in index order, preserving the lowest-index tie rule).
+//   * every block scans its whole support set: the scan only serves SMALL sets (< 512 points, ffb6d_knn_uses_pruning; larger
+//     ones are Morton-prepared and searched with tile pruning, knn_pruned.hip), at most one LDS tile, so there is nothing to split.
 //
-// Since knn_pruned.hip exists this scan only serves SMALL support sets (< 512 points since round 5, < 2048 before; larger ones
-// are Morton-prepared and searched with tile pruning) and the host-pointer cpp_knn* entry points
-// route through ffb6d_knn_batch_device, i.e. through whichever kernel fits the shape.
+// One kernel, knn_scan_multi_kernel: blockIdx.x walks the (search, frame, query block) triples of a table in the kernel
+// arguments.  ffb6d_knn_search_multi fills the table with all scans of a batch; ffb6d_knn_batch_device fills one entry.  The
+// host-pointer cpp_knn* entry points route through ffb6d_knn_batch_device, i.e. through whichever kernel fits the shape.
 //
 // Roofline: VALU-bound (8 f32 ops + compare per pair), algorithmic HBM traffic is ~10.7 MB/frame
 // (SURVEY.md section 8d).
-#include "common.h"
+#include "knn_common.h"
 
 #include <cfloat>
 #include <cmath>
@@ -74,15 +73,6 @@ struct TopK<1> {
     }
 };
 
-// squared distance with the reference's operation order, each op rounded to f32
-__device__ __forceinline__ float sqdist(float qx, float qy, float qz, const float4& p)
-{
-    const float dx = __fsub_rn(qx, p.x);
-    const float dy = __fsub_rn(qy, p.y);
-    const float dz = __fsub_rn(qz, p.z);
-    return __fadd_rn(__fadd_rn(__fmul_rn(dx, dx), __fmul_rn(dy, dy)), __fmul_rn(dz, dz));
-}
-
 template <int K>
 __device__ __forceinline__ void store_result(const TopK<K>& top, size_t row, int Kout,
                                              int64_t* __restrict__ idx64,
@@ -100,14 +90,13 @@ __device__ __forceinline__ void store_result(const TopK<K>& top, size_t row, int
     }
 }
 
-// grid = (ceil(Q / (256*QPT)), nsplit, B)
+// query block bx (256*QPT queries) of frame b against the whole support set of that frame
 template <int K, int QPT>
 __device__ __forceinline__ void
 knn_scan_body(const float* __restrict__ support, const float* __restrict__ query,
-              int S, int Q, int nsplit, int chunk,
-              float* __restrict__ part_d, uint32_t* __restrict__ part_i,
+              int S, int Q,
               int64_t* __restrict__ idx64, int32_t* __restrict__ idx32,
-              float* __restrict__ dist, int Kout, const int bx, const int split, const int b)
+              float* __restrict__ dist, int Kout, const int bx, const int b)
 {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     float4* tile = reinterpret_cast<float4*>(smem);
@@ -117,8 +106,6 @@ knn_scan_body(const float* __restrict__ support, const float* __restrict__ query
     const int q0 = bx * (KNN_BLOCK * QPT);
     const float* sup = support + (size_t)b * S * 3;
     const float* qry = query + (size_t)b * Q * 3;
-    const int s_begin = split * chunk;
-    const int s_end = min(S, s_begin + chunk);
 
     float qx[QPT], qy[QPT], qz[QPT], worst[QPT];
     int cnt[QPT];
@@ -151,8 +138,8 @@ knn_scan_body(const float* __restrict__ support, const float* __restrict__ query
         }
     };
 
-    for (int base = s_begin; base < s_end; base += KNN_TILE) {
-        const int n = min(KNN_TILE, s_end - base);
+    for (int base = 0; base < S; base += KNN_TILE) {
+        const int n = min(KNN_TILE, S - base);
         __syncthreads();  // every wave is done with the previous tile
 #pragma unroll
         for (int j = tid; j < KNN_TILE; j += KNN_BLOCK) {
@@ -179,7 +166,7 @@ knn_scan_body(const float* __restrict__ support, const float* __restrict__ query
 #pragma unroll
             for (int u = 0; u < KNN_GROUP; ++u)
 #pragma unroll
-                for (int t = 0; t < QPT; ++t) d[t][u] = sqdist(qx[t], qy[t], qz[t], p[u]);
+                for (int t = 0; t < QPT; ++t) d[t][u] = sqdist3(qx[t], qy[t], qz[t], p[u].x, p[u].y, p[u].z);
 #pragma unroll
             for (int u = 0; u < KNN_GROUP; ++u) {
                 const uint32_t sidx = __float_as_uint(p[u].w);   // global support index rides in .w
@@ -210,32 +197,12 @@ knn_scan_body(const float* __restrict__ support, const float* __restrict__ query
     for (int t = 0; t < QPT; ++t) {
         const int qi = q0 + t * KNN_BLOCK + tid;
         if (qi >= Q) continue;
-        if (nsplit == 1) {
-            store_result<K>(top[t], (size_t)b * Q + qi, Kout, idx64, idx32, dist);
-        } else {
-            const size_t o = (((size_t)b * nsplit + split) * Q + qi) * K;
-#pragma unroll
-            for (int k = 0; k < K; ++k) {
-                part_d[o + k] = top[t].d[k];
-                part_i[o + k] = top[t].i[k];
-            }
-        }
+        store_result<K>(top[t], (size_t)b * Q + qi, Kout, idx64, idx32, dist);
     }
 }
 
-template <int K, int QPT>
-__global__ void __launch_bounds__(KNN_BLOCK)
-knn_scan_kernel(const float* __restrict__ support, const float* __restrict__ query,
-                int S, int Q, int nsplit, int chunk,
-                float* __restrict__ part_d, uint32_t* __restrict__ part_i,
-                int64_t* __restrict__ idx64, int32_t* __restrict__ idx32,
-                float* __restrict__ dist, int Kout)
-{
-    knn_scan_body<K, QPT>(support, query, S, Q, nsplit, chunk, part_d, part_i, idx64, idx32, dist, Kout, blockIdx.x, blockIdx.y, blockIdx.z);
-}
-
-// several scans in ONE launch (ffb6d_knn_search_multi): blockIdx.x walks the (search, frame, query block) triples of a table
-// in the kernel arguments; every block scans its whole support (supports routed here are short: no split, no merge pass)
+// one or several scans in ONE launch: blockIdx.x walks the (search, frame, query block) triples of a table in the kernel
+// arguments
 struct ScanArgs {
     const float *support, *query;
     int64_t* idx64;
@@ -258,94 +225,10 @@ knn_scan_multi_kernel(const MultiScan m)
     for (int i = 1; i < MAX_SCANS; ++i) sidx += (i < m.n && m.a[i].blk0 <= (int)blockIdx.x) ? 1 : 0;
     const ScanArgs& a = m.a[sidx];
     const int local = blockIdx.x - a.blk0;
-    knn_scan_body<K, QPT>(a.support, a.query, a.S, a.Q, 1, a.S, nullptr, nullptr, a.idx64, a.idx32, a.dist, a.Kout, local % a.gx, 0,
-                          local / a.gx);
-}
-
-// merges the nsplit sorted partial lists of a query, in split (= index) order
-template <int K>
-__global__ void __launch_bounds__(KNN_BLOCK)
-knn_merge_kernel(const float* __restrict__ part_d, const uint32_t* __restrict__ part_i,
-                 int Q, int nsplit, int64_t* __restrict__ idx64, int32_t* __restrict__ idx32,
-                 float* __restrict__ dist, int Kout)
-{
-    const int qi = blockIdx.x * KNN_BLOCK + threadIdx.x;
-    const int b = blockIdx.y;
-    if (qi >= Q) return;
-    TopK<K> top;
-    top.init();
-    for (int s = 0; s < nsplit; ++s) {
-        const size_t o = (((size_t)b * nsplit + s) * Q + qi) * K;
-#pragma unroll
-        for (int k = 0; k < K; ++k) {
-            const float d = part_d[o + k];
-            if (d < top.d[K - 1]) top.insert(d, part_i[o + k]);
-        }
-    }
-    store_result<K>(top, (size_t)b * Q + qi, Kout, idx64, idx32, dist);
-}
-
-int pad_k(int K)
-{
-    int p = 1;
-    while (p < K) p <<= 1;
-    return p;
+    knn_scan_body<K, QPT>(a.support, a.query, a.S, a.Q, a.idx64, a.idx32, a.dist, a.Kout, local % a.gx, local / a.gx);
 }
 
 constexpr int qpt_for(int Kp) { return Kp == 1 ? 4 : (Kp <= 4 ? 2 : 1); }
-
-struct Plan {
-    int Kp, qpt, qblocks, nsplit, chunk;
-};
-
-Plan make_plan(int64_t B, int64_t S, int64_t Q, int K)
-{
-    Plan p;
-    p.Kp = pad_k(K);
-    p.qpt = qpt_for(p.Kp);
-    p.qblocks = (int)ceil_div(Q, (int64_t)KNN_BLOCK * p.qpt);
-    // aim at >= 4 blocks per CU (256 CUs); never split finer than 2 tiles per chunk
-    const int64_t target = 1024;
-    int64_t want = ceil_div(target, B * p.qblocks);
-    int64_t max_split = ceil_div(S, 2 * (int64_t)KNN_TILE);
-    int64_t ns = want < 1 ? 1 : want;
-    if (ns > max_split) ns = max_split;
-    if (ns > 64) ns = 64;
-    if (ns < 1) ns = 1;
-    int64_t chunk = ceil_div(S, ns);
-    chunk = ceil_div(chunk, (int64_t)KNN_TILE) * KNN_TILE;  // whole tiles
-    ns = ceil_div(S, chunk);
-    p.nsplit = (int)ns;
-    p.chunk = (int)chunk;
-    return p;
-}
-
-template <int K, int QPT>
-int launch_knn(const Plan& p, const float* support, const float* query, int64_t B, int64_t S,
-               int64_t Q, int Kout, int64_t* idx64, int32_t* idx32, float* dist, void* ws,
-               hipStream_t st)
-{
-    float* part_d = nullptr;
-    uint32_t* part_i = nullptr;
-    if (p.nsplit > 1) {
-        const size_t n = (size_t)B * p.nsplit * Q * K;
-        part_d = reinterpret_cast<float*>(ws);
-        part_i = reinterpret_cast<uint32_t*>(part_d + n);
-    }
-    const size_t lds = KNN_TILE * sizeof(float4) +
-                       (K > 1 ? (size_t)QPT * KNN_QCAP * KNN_BLOCK * sizeof(uint2) : 0);
-    dim3 grid(p.qblocks, p.nsplit, (unsigned)B);
-    hipLaunchKernelGGL((knn_scan_kernel<K, QPT>), grid, dim3(KNN_BLOCK), lds, st, support, query,
-                       (int)S, (int)Q, p.nsplit, p.chunk, part_d, part_i, idx64, idx32, dist, Kout);
-    FFB6D_LAUNCH_CHECK();
-    if (p.nsplit > 1) {
-        dim3 mgrid((unsigned)ceil_div(Q, KNN_BLOCK), (unsigned)B);
-        hipLaunchKernelGGL((knn_merge_kernel<K>), mgrid, dim3(KNN_BLOCK), 0, st, part_d, part_i,
-                           (int)Q, p.nsplit, idx64, idx32, dist, Kout);
-        FFB6D_LAUNCH_CHECK();
-    }
-    return FFB6D_OK;
-}
 
 int check_shape(int64_t B, int64_t S, int64_t Q, int64_t dim, int64_t K)
 {
@@ -410,6 +293,37 @@ int launch_scan_multi(const MultiScan& m, int blocks, hipStream_t st)
     return FFB6D_OK;
 }
 
+// The scans of one padded K, collected into tables of MAX_SCANS and launched table by table.
+struct ScanBatch {
+    int kp;
+    int64_t B;
+    hipStream_t st;
+    MultiScan m;
+    int64_t blocks;
+
+    ScanBatch(int kp_, int64_t B_, hipStream_t st_) : kp(kp_), B(B_), st(st_), blocks(0) { m.n = 0; }
+
+    int flush()
+    {
+        if (m.n == 0) return FFB6D_OK;
+        const int rc = dispatch_padded_k(kp, [&](auto k) { return launch_scan_multi<decltype(k)::value>(m, (int)blocks, st); });
+        m.n = 0;
+        blocks = 0;
+        return rc;
+    }
+
+    int add(const ffb6d_knn_search_t& s)
+    {
+        ScanArgs& a = m.a[m.n];
+        a.support = s.support; a.query = s.query; a.idx64 = s.idx64; a.idx32 = s.idx32; a.dist = s.dist;
+        a.S = (int)s.S; a.Q = (int)s.Q; a.Kout = s.K;
+        a.gx = (int)ceil_div(s.Q, (int64_t)KNN_BLOCK * qpt_for(kp));
+        a.blk0 = (int)blocks;
+        if (const int rc = add_blocks(blocks, a.gx, B)) return rc;
+        return ++m.n == MAX_SCANS ? flush() : FFB6D_OK;
+    }
+};
+
 }  // namespace
 
 int knn_search_multi_prepared(const ffb6d_knn_search_t* s, const int* which, int n, int64_t B, hipStream_t st);   // knn_pruned.hip
@@ -442,36 +356,10 @@ extern "C" int ffb6d_knn_search_multi(int n, const ffb6d_knn_search_t* s, int64_
     int rc = FFB6D_OK;
     const int kps[6] = {1, 2, 4, 8, 16, 32};
     for (int kp : kps) {
-        MultiScan m;
-        m.n = 0;
-        int blocks = 0;
-        auto flush = [&]() -> int {
-            if (m.n == 0) return FFB6D_OK;
-            int r = FFB6D_OK;
-            hipStream_t ls = st;
-            switch (kp) {
-                case 1: r = launch_scan_multi<1>(m, blocks, ls); break;
-                case 2: r = launch_scan_multi<2>(m, blocks, ls); break;
-                case 4: r = launch_scan_multi<4>(m, blocks, ls); break;
-                case 8: r = launch_scan_multi<8>(m, blocks, ls); break;
-                case 16: r = launch_scan_multi<16>(m, blocks, ls); break;
-                default: r = launch_scan_multi<32>(m, blocks, ls); break;
-            }
-            m.n = 0;
-            blocks = 0;
-            return r;
-        };
-        for (int i = 0; i < n && rc == FFB6D_OK; ++i) {
-            if (ffb6d_knn_uses_pruning(B, s[i].S, s[i].Q, s[i].K) || pad_k(s[i].K) != kp) continue;
-            ScanArgs& a = m.a[m.n];
-            a.support = s[i].support; a.query = s[i].query; a.idx64 = s[i].idx64; a.idx32 = s[i].idx32; a.dist = s[i].dist;
-            a.S = (int)s[i].S; a.Q = (int)s[i].Q; a.Kout = s[i].K;
-            a.gx = (int)ceil_div(s[i].Q, (int64_t)KNN_BLOCK * qpt_for(kp));
-            a.blk0 = blocks;
-            blocks += a.gx * (int)B;
-            if (++m.n == MAX_SCANS) rc = flush();
-        }
-        if (rc == FFB6D_OK) rc = flush();
+        ScanBatch batch(kp, B, st);
+        for (int i = 0; i < n && rc == FFB6D_OK; ++i)
+            if (!ffb6d_knn_uses_pruning(B, s[i].S, s[i].Q, s[i].K) && pad_k(s[i].K) == kp) rc = batch.add(s[i]);
+        if (rc == FFB6D_OK) rc = batch.flush();
         if (rc != FFB6D_OK) break;
     }
     if (rc == FFB6D_OK) rc = knn_search_multi_prepared(s, pruned, np, B, st);
@@ -494,13 +382,9 @@ static size_t align256(size_t v) { return (v + 255) / 256 * 256; }
 size_t ffb6d_knn_workspace_bytes(int64_t B, int64_t S, int64_t Q, int K)
 {
     if (B <= 0 || S <= 0 || Q <= 0 || K < 1 || K > 32) return 0;
-    if (ffb6d_knn_uses_pruning(B, S, Q, K)) {
-        return align256(ffb6d_knn_prepared_bytes(B, S)) + align256(ffb6d_knn_prepared_bytes(B, Q)) +
-               align256(ffb6d_knn_prepare_workspace_bytes(B, S > Q ? S : Q));
-    }
-    const Plan p = make_plan(B, S, Q, K);
-    if (p.nsplit <= 1) return 0;
-    return (size_t)B * p.nsplit * Q * p.Kp * (sizeof(float) + sizeof(uint32_t));
+    if (!ffb6d_knn_uses_pruning(B, S, Q, K)) return 0;   // the scan keeps everything in registers and LDS
+    return align256(ffb6d_knn_prepared_bytes(B, S)) + align256(ffb6d_knn_prepared_bytes(B, Q)) +
+           align256(ffb6d_knn_prepare_workspace_bytes(B, S > Q ? S : Q));
 }
 
 int ffb6d_knn_batch_device(const float* support, const float* query, int64_t B, int64_t S,
@@ -534,17 +418,11 @@ int ffb6d_knn_batch_device(const float* support, const float* query, int64_t B, 
         }
         return ffb6d_knn_search_prepared(prep_s, prep_q, nullptr, B, S, Q, K, idx64, idx32, dist, stream);
     }
-    const Plan p = make_plan(B, S, Q, K);
-    hipStream_t st = as_stream(stream);
-    switch (p.Kp) {
-        case 1:  return launch_knn<1, qpt_for(1)>(p, support, query, B, S, Q, K, idx64, idx32, dist, workspace, st);
-        case 2:  return launch_knn<2, qpt_for(2)>(p, support, query, B, S, Q, K, idx64, idx32, dist, workspace, st);
-        case 4:  return launch_knn<4, qpt_for(4)>(p, support, query, B, S, Q, K, idx64, idx32, dist, workspace, st);
-        case 8:  return launch_knn<8, qpt_for(8)>(p, support, query, B, S, Q, K, idx64, idx32, dist, workspace, st);
-        case 16: return launch_knn<16, qpt_for(16)>(p, support, query, B, S, Q, K, idx64, idx32, dist, workspace, st);
-        case 32: return launch_knn<32, qpt_for(32)>(p, support, query, B, S, Q, K, idx64, idx32, dist, workspace, st);
-    }
-    return set_error(FFB6D_ERR_ARG, "knn: unsupported K=%d", K);
+    // short support: one entry in the table of the scan kernel
+    const ffb6d_knn_search_t one = {nullptr, nullptr, support, query, S, Q, K, idx64, idx32, dist};
+    ScanBatch batch(pad_k(K), B, as_stream(stream));
+    rc = batch.add(one);
+    return rc == FFB6D_OK ? batch.flush() : rc;
 }
 
 void cpp_knn(const float* points, const size_t npts, const size_t dim, const float* queries,

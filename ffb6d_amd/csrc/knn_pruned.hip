@@ -22,7 +22,11 @@
 // <= the rounded distance of every point in the box; tiles with bound <= current K-th distance
 // are always entered; candidates are compared as (distance, original index) pairs, so the
 // visiting order cannot change which neighbour wins a tie.
-#include "common.h"
+//
+// Every step exists once, as a kernel that takes a table in its arguments: several point sets per prepare
+// (ffb6d_knn_prepare_multi), several searches per launch (ffb6d_knn_search_multi).  The single calls ffb6d_knn_prepare and
+// ffb6d_knn_search_prepared run the same kernels with a table of one.
+#include "knn_common.h"
 
 #include <rocprim/rocprim.hpp>      // 64-bit sort keys only (more than 256 (set, frame) segments in one call)
 
@@ -148,12 +152,6 @@ __device__ __forceinline__ void frame_body(const float* __restrict__ pts, int S,
     if (threadIdx.x == 3) { frame[b * 8 + 3] = 0.f; frame[b * 8 + 7] = 0.f; }
 }
 
-__global__ void __launch_bounds__(1024)
-frame_kernel(const float* __restrict__ pts, int S, float* __restrict__ frame)
-{
-    frame_body(pts, S, frame, blockIdx.x);
-}
-
 __device__ __forceinline__ uint32_t spread10(uint32_t v)
 {
     v &= 0x3ffu;
@@ -184,13 +182,6 @@ __device__ __forceinline__ void morton_body(const float* __restrict__ pts, int S
     const uint32_t k = morton_key(p[0], p[1], p[2], frame + b * 8);
     keys[(size_t)b * S + i] = ((KeyT)seg << SORT_BITS) | (KeyT)(k >> SORT_DROP);
     vals[(size_t)b * S + i] = (uint32_t)i;
-}
-
-template <typename KeyT>
-__global__ void __launch_bounds__(BLK)
-morton_kernel(const float* __restrict__ pts, int S, const float* __restrict__ frame, KeyT* __restrict__ keys, uint32_t* __restrict__ vals)
-{
-    morton_body(pts, S, frame, keys, vals, blockIdx.y, blockIdx.y);
 }
 
 // one wave per tile: gather the sorted points, build the tile box
@@ -230,15 +221,6 @@ __device__ __forceinline__ void gather_box_body(const float* __restrict__ pts, i
     }
 }
 
-template <typename KeyT>
-__global__ void __launch_bounds__(BLK)
-gather_box_kernel(const float* __restrict__ pts, int S, int S_pad, int nt,
-                  const KeyT* __restrict__ skeys, const uint32_t* __restrict__ perm,
-                  float4* __restrict__ out_pts, float4* __restrict__ boxes, uint32_t* __restrict__ out_keys)
-{
-    gather_box_body(pts, S, S_pad, nt, skeys, perm, out_pts, boxes, out_keys, blockIdx.y);
-}
-
 // level-2 boxes: the hull of FAN consecutive tile boxes
 __device__ __forceinline__ void box2_body(const float4* __restrict__ boxes, int nt, int nt2, float4* __restrict__ boxes2, int b)
 {
@@ -252,12 +234,6 @@ __device__ __forceinline__ void box2_body(const float4* __restrict__ boxes, int 
     }
     boxes2[((size_t)b * nt2 + g) * 2] = lo;
     boxes2[((size_t)b * nt2 + g) * 2 + 1] = hi;
-}
-
-__global__ void __launch_bounds__(BLK)
-box2_kernel(const float4* __restrict__ boxes, int nt, int nt2, float4* __restrict__ boxes2)
-{
-    box2_body(boxes, nt, nt2, boxes2, blockIdx.y);
 }
 
 // cell -> index of the tile that holds the first point whose key is >= (cell << CELL_SHIFT)
@@ -276,16 +252,10 @@ __device__ __forceinline__ void cell_table_body(const uint32_t* __restrict__ key
     table[(size_t)b * NCELL + c] = (uint32_t)min(lo / PT, nt - 1);
 }
 
-__global__ void __launch_bounds__(BLK)
-cell_table_kernel(const uint32_t* __restrict__ keys, int S, int S_pad, int nt, uint32_t* __restrict__ table)
-{
-    cell_table_body(keys, S, S_pad, nt, table, blockIdx.y);
-}
-
-// ---- several point sets in one go (the 22 searches of an index pyramid touch a handful of sets, all known up front:
-// linemod_dataset.py:299-353): blockIdx.z = set, the kernels above with one more grid dimension, and ONE radix sort over the
-// concatenation of all sets with the sort segment (set, frame) in the key's high bits -- a handful of launches instead of
-// a dozen per set, and the sort's fixed costs are paid once.
+// ---- the kernels: one or several point sets in one go (the 22 searches of an index pyramid touch a handful of sets, all known
+// up front: linemod_dataset.py:299-353): blockIdx.z = set, blockIdx.y = frame, and ONE radix sort over the concatenation of all
+// sets with the sort segment (set, frame) in the key's high bits -- a handful of launches instead of a dozen per set, and the
+// sort's fixed costs are paid once.  ffb6d_knn_prepare is the same call with one set.
 constexpr int MAX_SETS = 8;
 struct SetDesc {
     const float* pts;
@@ -370,12 +340,6 @@ struct TopKL {
     }
 };
 
-__device__ __forceinline__ float sqdist3(float qx, float qy, float qz, float px, float py, float pz)
-{
-    const float dx = __fsub_rn(qx, px), dy = __fsub_rn(qy, py), dz = __fsub_rn(qz, pz);
-    return __fadd_rn(__fadd_rn(__fmul_rn(dx, dx), __fmul_rn(dy, dy)), __fmul_rn(dz, dz));
-}
-
 // lower bound of sqdist3(q, p) over all p inside [lo, hi]; same op order, monotone rounding
 __device__ __forceinline__ float box_bound(float qx, float qy, float qz, const float4& lo, const float4& hi)
 {
@@ -413,15 +377,14 @@ __device__ __forceinline__ float wave_min(float v)
     return v;
 }
 
-// grid = (ceil(Q_pad / 256), B); queries come Morton ordered with their original index in .w.
+// query block blk_x (256 slots of Q_pad) of frame b; queries come Morton ordered with their original index in .w.
 // Each wave works on its own: 64 neighbouring queries, tiles tested 64 at a time (one tile box
 // per lane against the wave's query box), surviving tiles fetched with one coalesced load and
 // broadcast through a wave-private LDS slice.
 template <int K>
 __device__ __forceinline__ void
 knn_pruned_body(const float4* __restrict__ spts, const float4* __restrict__ boxes,
-                const uint32_t* __restrict__ skeys, const float* __restrict__ sframe,
-                const uint32_t* __restrict__ scell, int S, int S_pad, int nt,
+                const float* __restrict__ sframe, const uint32_t* __restrict__ scell, int S, int S_pad, int nt,
                 const float4* __restrict__ qpts, int Q, int Q_pad,
                 int64_t* __restrict__ idx64, int32_t* __restrict__ idx32, float* __restrict__ dist,
                 int Kout, const int blk_x, const int b)
@@ -589,7 +552,7 @@ knn_pruned_body(const float4* __restrict__ spts, const float4* __restrict__ boxe
 //     4 coalesced 256-byte row loads.  Every lane does useful work whether the queries of a
 //     wave are neighbours in space or not, so sparse query sets (a few hundred points against
 //     a 76800-pixel grid) cost the same per query as dense ones.
-// grid = (ceil(Q_pad / 16), B)
+// query block blk_x (16 queries) of frame b
 // ------------------------------------------------------------------------------------------
 __device__ __forceinline__ uint32_t row_bits(unsigned long long ballot, int lane)
 {
@@ -737,10 +700,10 @@ knn_row16_body(const float4* __restrict__ spts, const float4* __restrict__ boxes
     }
 }
 
-// ---- kernels: one search per launch (grid = (query blocks, B)), or several searches in ONE launch -- the searches of an
-// index pyramid read only the cloud and the xyz image, none depends on another (linemod_dataset.py:299-353), so all searches
-// that run the same kernel go out together: blockIdx.x walks the (search, frame, query block) triples of a table in the
-// kernel arguments.
+// ---- kernels: one or several searches in ONE launch -- the searches of an index pyramid read only the cloud and the xyz
+// image, none depends on another (linemod_dataset.py:299-353), so all searches that run the same kernel go out together:
+// blockIdx.x walks the (search, frame, query block) triples of a table in the kernel arguments.  A single call
+// (ffb6d_knn_search_prepared) is a table with one entry.
 struct PrunedArgs {
     const float4 *spts, *boxes, *boxes2, *qpts;
     const uint32_t *skeys, *scell;
@@ -769,37 +732,12 @@ __device__ __forceinline__ int find_search(const MultiPruned& m, int blk)
 
 template <int K>
 __global__ void __launch_bounds__(BLK)
-knn_pruned_kernel(const float4* __restrict__ spts, const float4* __restrict__ boxes,
-                  const uint32_t* __restrict__ skeys, const float* __restrict__ sframe,
-                  const uint32_t* __restrict__ scell, int S, int S_pad, int nt,
-                  const float4* __restrict__ qpts, int Q, int Q_pad,
-                  int64_t* __restrict__ idx64, int32_t* __restrict__ idx32, float* __restrict__ dist,
-                  int Kout)
-{
-    knn_pruned_body<K>(spts, boxes, skeys, sframe, scell, S, S_pad, nt, qpts, Q, Q_pad, idx64, idx32, dist, Kout, blockIdx.x, blockIdx.y);
-}
-
-template <int K>
-__global__ void __launch_bounds__(BLK)
 knn_pruned_multi_kernel(const MultiPruned m)
 {
     const PrunedArgs& a = m.a[find_search(m, blockIdx.x)];
     const int local = blockIdx.x - a.blk0;
-    knn_pruned_body<K>(a.spts, a.boxes, a.skeys, a.sframe, a.scell, a.S, a.S_pad, a.nt, a.qpts, a.Q, a.Q_pad, a.idx64, a.idx32, a.dist,
+    knn_pruned_body<K>(a.spts, a.boxes, a.sframe, a.scell, a.S, a.S_pad, a.nt, a.qpts, a.Q, a.Q_pad, a.idx64, a.idx32, a.dist,
                        a.Kout, local % a.gx, local / a.gx);
-}
-
-template <int K>
-__global__ void __launch_bounds__(BLK)
-knn_row16_kernel(const float4* __restrict__ spts, const float4* __restrict__ boxes,
-                 const float4* __restrict__ boxes2, const float* __restrict__ sframe,
-                 const uint32_t* __restrict__ skeys, int S, int S_pad, int nt, int nt2,
-                 const float4* __restrict__ qpts, const float* __restrict__ qraw, int Q, int Q_pad,
-                 int64_t* __restrict__ idx64, int32_t* __restrict__ idx32, float* __restrict__ dist,
-                 int Kout)
-{
-    knn_row16_body<K>(spts, boxes, boxes2, sframe, skeys, S, S_pad, nt, nt2, qpts, qraw, Q, Q_pad, idx64, idx32, dist, Kout,
-                      blockIdx.x, blockIdx.y);
 }
 
 template <int K>
@@ -810,13 +748,6 @@ knn_row16_multi_kernel(const MultiPruned m)
     const int local = blockIdx.x - a.blk0;
     knn_row16_body<K>(a.spts, a.boxes, a.boxes2, a.sframe, a.skeys, a.S, a.S_pad, a.nt, a.nt2, a.qpts, a.qraw, a.Q, a.Q_pad, a.idx64,
                       a.idx32, a.dist, a.Kout, local % a.gx, local / a.gx);
-}
-
-int pad_k(int K)
-{
-    int p = 1;
-    while (p < K) p <<= 1;
-    return p;
 }
 
 size_t sort_temp_bound(size_t n, size_t sort_blocks)
@@ -878,7 +809,130 @@ PrepWs prep_ws_n(size_t n, size_t sort_blocks)
     return w;
 }
 
+// Morton-prepares nsets point sets of B frames each (see the kernels above); `who` names the entry point in error messages.
+int prepare_sets(const char* who, int nsets, const float* const* pts, const int64_t* npts, int64_t B, void* const* prepared,
+                 const size_t* prepared_bytes, void* workspace, size_t workspace_bytes, hipStream_t st)
+{
+    MultiDesc m;
+    m.B = (int)B;
+    segsort::Plan plan;
+    plan.ngroups = nsets; plan.B = (int)B;
+    size_t n = 0, sort_blocks = 0;
+    int64_t S_max = 0, nt_max = 0, nt2_max = 0;
+    for (int i = 0; i < nsets; ++i) {
+        FFB6D_REQUIRE(npts[i] >= 1 && npts[i] < (1LL << 31) && pts[i] && prepared[i], "%s: set %d is empty or null", who, i);
+        const Layout L = layout(B, npts[i]);
+        if (prepared_bytes[i] < L.total)
+            return set_error(FFB6D_ERR_WORKSPACE, "%s: set %d needs %zu prepared bytes, got %zu", who, i, L.total, prepared_bytes[i]);
+        char* pp = static_cast<char*>(prepared[i]);
+        SetDesc& d = m.s[i];
+        d.pts = pts[i];
+        d.out_pts = reinterpret_cast<float4*>(pp + L.pts_off);
+        d.boxes = reinterpret_cast<float4*>(pp + L.box_off);
+        d.boxes2 = reinterpret_cast<float4*>(pp + L.box2_off);
+        d.out_keys = reinterpret_cast<uint32_t*>(pp + L.key_off);
+        d.cell = reinterpret_cast<uint32_t*>(pp + L.cell_off);
+        d.frame = reinterpret_cast<float*>(pp + L.frame_off);
+        d.S = (int)npts[i]; d.S_pad = (int)L.S_pad; d.nt = (int)L.nt; d.nt2 = (int)L.nt2;
+        d.pos0 = (long long)n;
+        plan.g[i].pos0 = d.pos0; plan.g[i].S = d.S;
+        n += (size_t)B * (size_t)npts[i];
+        sort_blocks += (size_t)B * (size_t)ceil_div(npts[i], segsort::CHUNK);
+        S_max = std::max<int64_t>(S_max, npts[i]); nt_max = std::max<int64_t>(nt_max, L.nt); nt2_max = std::max<int64_t>(nt2_max, L.nt2);
+    }
+    const PrepWs W = prep_ws_n(n, sort_blocks);
+    if (workspace_bytes < W.total) return set_error(FFB6D_ERR_WORKSPACE, "%s: need %zu workspace bytes, got %zu", who, W.total, workspace_bytes);
+    char* ws = static_cast<char*>(workspace);
+    auto* keys_in = reinterpret_cast<unsigned long long*>(ws + W.keys_in);
+    auto* keys_out = reinterpret_cast<unsigned long long*>(ws + W.keys_out);
+    auto* vals_in = reinterpret_cast<uint32_t*>(ws + W.vals_in);
+    auto* vals_out = reinterpret_cast<uint32_t*>(ws + W.vals_out);
+    const unsigned ns = (unsigned)nsets, nb = (unsigned)B;
+    hipLaunchKernelGGL(frame_multi_kernel, dim3(nb, ns), dim3(1024), 0, st, m);
+    auto run = [&](auto* kin, auto* kout) -> int {
+        using KeyT = std::remove_pointer_t<decltype(kin)>;
+        hipLaunchKernelGGL((morton_multi_kernel<KeyT>), dim3((unsigned)ceil_div(S_max, BLK), nb, ns), dim3(BLK), 0, st, m, kin, vals_in);
+        FFB6D_LAUNCH_CHECK();
+        if (const int rc = sort_segments(kin, kout, vals_in, vals_out, n, B * nsets, plan, ws + W.temp, W.temp_bytes, st, who)) return rc;
+        hipLaunchKernelGGL((gather_box_multi_kernel<KeyT>), dim3((unsigned)ceil_div(nt_max, BLK / 64), nb, ns), dim3(BLK), 0, st, m, kout,
+                           vals_out);
+        return FFB6D_OK;
+    };
+    const int rc = B * nsets <= MAX_SEG32 ? run(reinterpret_cast<uint32_t*>(keys_in), reinterpret_cast<uint32_t*>(keys_out))
+                                          : run(keys_in, keys_out);
+    if (rc) return rc;
+    hipLaunchKernelGGL(box2_multi_kernel, dim3((unsigned)ceil_div(nt2_max, BLK), nb, ns), dim3(BLK), 0, st, m);
+    hipLaunchKernelGGL(cell_table_multi_kernel, dim3(NCELL / BLK, nb, ns), dim3(BLK), 0, st, m);
+    FFB6D_LAUNCH_CHECK();
+    return FFB6D_OK;
+}
+
+template <int K>
+int launch_search_multi(const MultiPruned& m, int blocks, hipStream_t st)
+{
+    if constexpr (K == 1 || K == 32) {   // a lane per query: wave-private tile slice, and for K > 1 the per-lane candidate queue
+        const size_t lds = (size_t)(BLK / 64) * PT * sizeof(float4) + (K > 1 ? (size_t)QCAP * BLK * sizeof(uint2) : 0);
+        hipLaunchKernelGGL((knn_pruned_multi_kernel<K>), dim3((unsigned)blocks), dim3(BLK), lds, st, m);
+    } else {                             // a row of 16 lanes per query
+        hipLaunchKernelGGL((knn_row16_multi_kernel<K>), dim3((unsigned)blocks), dim3(BLK), 0, st, m);
+    }
+    FFB6D_LAUNCH_CHECK();
+    return FFB6D_OK;
+}
+
 }  // namespace
+
+// Searches of `s` (indices `which`, all routed to the Morton-ordered kernels) in as few launches as kernels: one per padded K
+// of the 16-lane row kernel, one for K = 1, one for K > 16.  Called by ffb6d_knn_search_multi (csrc/knn.hip) and, with one
+// search, by ffb6d_knn_search_prepared.
+int knn_search_multi_prepared(const ffb6d_knn_search_t* s, const int* which, int n, int64_t B, hipStream_t st)
+{
+    const int kps[6] = {1, 2, 4, 8, 16, 32};
+    for (int kp : kps) {
+        MultiPruned m;
+        m.n = 0;
+        int64_t blocks = 0;
+        auto flush = [&]() -> int {
+            if (m.n == 0) return FFB6D_OK;
+            const int rc = dispatch_padded_k(kp, [&](auto k) { return launch_search_multi<decltype(k)::value>(m, (int)blocks, st); });
+            m.n = 0;
+            blocks = 0;
+            return rc;
+        };
+        const bool row = kp >= 2 && kp <= 16;
+        for (int w = 0; w < n; ++w) {
+            const ffb6d_knn_search_t& q = s[which[w]];
+            if (pad_k(q.K) != kp) continue;
+            FFB6D_REQUIRE(q.prep_support && (q.prep_query || (q.query && row)), "knn_search_multi: search %d needs a prepared support "
+                          "and prepared (K = 1, K > 16) or raw (2 <= K <= 16) queries", which[w]);
+            const Layout LS = layout(B, q.S), LQ = layout(B, q.Q);
+            const char* ps = static_cast<const char*>(q.prep_support);
+            const char* pq = static_cast<const char*>(q.prep_query);
+            PrunedArgs& a = m.a[m.n];
+            a.spts = reinterpret_cast<const float4*>(ps + LS.pts_off);
+            a.boxes = reinterpret_cast<const float4*>(ps + LS.box_off);
+            a.boxes2 = reinterpret_cast<const float4*>(ps + LS.box2_off);
+            a.skeys = reinterpret_cast<const uint32_t*>(ps + LS.key_off);
+            a.sframe = reinterpret_cast<const float*>(ps + LS.frame_off);
+            a.scell = reinterpret_cast<const uint32_t*>(ps + LS.cell_off);
+            a.qpts = pq ? reinterpret_cast<const float4*>(pq + LQ.pts_off) : nullptr;
+            a.qraw = pq ? nullptr : q.query;
+            a.idx64 = q.idx64; a.idx32 = q.idx32; a.dist = q.dist;
+            a.S = (int)q.S; a.S_pad = (int)LS.S_pad; a.nt = (int)LS.nt; a.nt2 = (int)LS.nt2;
+            a.Q = (int)q.Q; a.Q_pad = (int)LQ.S_pad; a.Kout = q.K;
+            a.gx = (int)ceil_div(LQ.S_pad, row ? BLK / 16 : BLK);
+            a.blk0 = (int)blocks;
+            if (const int rc = add_blocks(blocks, a.gx, B)) return rc;
+            if (++m.n == MAX_SEARCHES) {
+                const int rc = flush();
+                if (rc != FFB6D_OK) return rc;
+            }
+        }
+        const int rc = flush();
+        if (rc != FFB6D_OK) return rc;
+    }
+    return FFB6D_OK;
+}
 }  // namespace ffb6d
 
 using namespace ffb6d;
@@ -903,45 +957,11 @@ int ffb6d_knn_prepare(const float* pts, int64_t B, int64_t S, void* prepared, si
     FFB6D_REQUIRE(B >= 1 && S >= 1, "knn_prepare: empty point set");
     FFB6D_REQUIRE(S < (1LL << 31) && B < 65536, "knn_prepare: size too large");
     FFB6D_REQUIRE(pts && prepared && workspace, "knn_prepare: null pointer");
-    const Layout L = layout(B, S);
-    const PrepWs W = prep_ws(B, S);
-    if (prepared_bytes < L.total || workspace_bytes < W.total)
+    const size_t need_p = layout(B, S).total, need_w = prep_ws(B, S).total;
+    if (prepared_bytes < need_p || workspace_bytes < need_w)
         return set_error(FFB6D_ERR_WORKSPACE, "knn_prepare: need %zu prepared + %zu workspace bytes, got %zu + %zu",
-                         L.total, W.total, prepared_bytes, workspace_bytes);
-    hipStream_t st = as_stream(stream);
-    char* ws = static_cast<char*>(workspace);
-    char* pp = static_cast<char*>(prepared);
-    auto* keys_in = reinterpret_cast<unsigned long long*>(ws + W.keys_in);
-    auto* keys_out = reinterpret_cast<unsigned long long*>(ws + W.keys_out);
-    auto* vals_in = reinterpret_cast<uint32_t*>(ws + W.vals_in);
-    auto* vals_out = reinterpret_cast<uint32_t*>(ws + W.vals_out);
-    float* frame = reinterpret_cast<float*>(pp + L.frame_off);
-
-    hipLaunchKernelGGL(frame_kernel, dim3((unsigned)B), dim3(1024), 0, st, pts, (int)S, frame);
-    const size_t n = (size_t)B * S;
-    auto run = [&](auto* kin, auto* kout) -> int {
-        using KeyT = std::remove_pointer_t<decltype(kin)>;
-        hipLaunchKernelGGL((morton_kernel<KeyT>), dim3((unsigned)ceil_div(S, BLK), (unsigned)B), dim3(BLK), 0, st, pts, (int)S, frame, kin,
-                           vals_in);
-        FFB6D_LAUNCH_CHECK();
-        segsort::Plan plan;
-        plan.ngroups = 1; plan.B = (int)B; plan.g[0].pos0 = 0; plan.g[0].S = (int)S;
-        if (const int rc = sort_segments(kin, kout, vals_in, vals_out, n, B, plan, ws + W.temp, W.temp_bytes, st, "knn_prepare")) return rc;
-        hipLaunchKernelGGL((gather_box_kernel<KeyT>), dim3((unsigned)ceil_div(L.nt, BLK / 64), (unsigned)B), dim3(BLK), 0, st, pts,
-                           (int)S, (int)L.S_pad, (int)L.nt, kout, vals_out, reinterpret_cast<float4*>(pp + L.pts_off),
-                           reinterpret_cast<float4*>(pp + L.box_off), reinterpret_cast<uint32_t*>(pp + L.key_off));
-        return FFB6D_OK;
-    };
-    const int rc = B <= MAX_SEG32 ? run(reinterpret_cast<uint32_t*>(keys_in), reinterpret_cast<uint32_t*>(keys_out)) : run(keys_in, keys_out);
-    if (rc) return rc;
-    hipLaunchKernelGGL(box2_kernel, dim3((unsigned)ceil_div(L.nt2, BLK), (unsigned)B), dim3(BLK), 0, st,
-                       reinterpret_cast<const float4*>(pp + L.box_off), (int)L.nt, (int)L.nt2,
-                       reinterpret_cast<float4*>(pp + L.box2_off));
-    hipLaunchKernelGGL(cell_table_kernel, dim3(NCELL / BLK, (unsigned)B), dim3(BLK), 0, st,
-                       reinterpret_cast<const uint32_t*>(pp + L.key_off), (int)S, (int)L.S_pad, (int)L.nt,
-                       reinterpret_cast<uint32_t*>(pp + L.cell_off));
-    FFB6D_LAUNCH_CHECK();
-    return FFB6D_OK;
+                         need_p, need_w, prepared_bytes, workspace_bytes);
+    return prepare_sets("knn_prepare", 1, &pts, &S, B, &prepared, &prepared_bytes, workspace, workspace_bytes, as_stream(stream));
 }
 
 size_t ffb6d_knn_prepare_multi_workspace_bytes(int nsets, const int64_t* npts, int64_t B)
@@ -962,64 +982,7 @@ int ffb6d_knn_prepare_multi(int nsets, const float* const* pts, const int64_t* n
     FFB6D_REQUIRE(nsets >= 1 && nsets <= MAX_SETS, "knn_prepare_multi: 1..%d sets per call (got %d)", MAX_SETS, nsets);
     FFB6D_REQUIRE(pts && npts && prepared && prepared_bytes && workspace, "knn_prepare_multi: null pointer");
     FFB6D_REQUIRE(B >= 1 && B * (int64_t)nsets < 65536, "knn_prepare_multi: bad batch size");
-    MultiDesc m;
-    m.B = (int)B;
-    size_t n = 0;
-    int64_t S_max = 0, nt_max = 0, nt2_max = 0;
-    for (int i = 0; i < nsets; ++i) {
-        FFB6D_REQUIRE(npts[i] >= 1 && npts[i] < (1LL << 31) && pts[i] && prepared[i], "knn_prepare_multi: set %d is empty or null", i);
-        const Layout L = layout(B, npts[i]);
-        if (prepared_bytes[i] < L.total)
-            return set_error(FFB6D_ERR_WORKSPACE, "knn_prepare_multi: set %d needs %zu prepared bytes, got %zu", i, L.total, prepared_bytes[i]);
-        char* pp = static_cast<char*>(prepared[i]);
-        SetDesc& d = m.s[i];
-        d.pts = pts[i];
-        d.out_pts = reinterpret_cast<float4*>(pp + L.pts_off);
-        d.boxes = reinterpret_cast<float4*>(pp + L.box_off);
-        d.boxes2 = reinterpret_cast<float4*>(pp + L.box2_off);
-        d.out_keys = reinterpret_cast<uint32_t*>(pp + L.key_off);
-        d.cell = reinterpret_cast<uint32_t*>(pp + L.cell_off);
-        d.frame = reinterpret_cast<float*>(pp + L.frame_off);
-        d.S = (int)npts[i]; d.S_pad = (int)L.S_pad; d.nt = (int)L.nt; d.nt2 = (int)L.nt2;
-        d.pos0 = (long long)n;
-        n += (size_t)B * (size_t)npts[i];
-        S_max = std::max<int64_t>(S_max, npts[i]); nt_max = std::max<int64_t>(nt_max, L.nt); nt2_max = std::max<int64_t>(nt2_max, L.nt2);
-    }
-    segsort::Plan plan;
-    plan.ngroups = nsets; plan.B = (int)B;
-    size_t sort_blocks = 0;
-    for (int i = 0; i < nsets; ++i) {
-        plan.g[i].pos0 = m.s[i].pos0; plan.g[i].S = m.s[i].S;
-        sort_blocks += (size_t)B * (size_t)ceil_div(npts[i], segsort::CHUNK);
-    }
-    const PrepWs W = prep_ws_n(n, sort_blocks);
-    if (workspace_bytes < W.total)
-        return set_error(FFB6D_ERR_WORKSPACE, "knn_prepare_multi: need %zu workspace bytes, got %zu", W.total, workspace_bytes);
-    hipStream_t st = as_stream(stream);
-    char* ws = static_cast<char*>(workspace);
-    auto* keys_in = reinterpret_cast<unsigned long long*>(ws + W.keys_in);
-    auto* keys_out = reinterpret_cast<unsigned long long*>(ws + W.keys_out);
-    auto* vals_in = reinterpret_cast<uint32_t*>(ws + W.vals_in);
-    auto* vals_out = reinterpret_cast<uint32_t*>(ws + W.vals_out);
-    const unsigned ns = (unsigned)nsets, nb = (unsigned)B;
-    hipLaunchKernelGGL(frame_multi_kernel, dim3(nb, ns), dim3(1024), 0, st, m);
-    auto run = [&](auto* kin, auto* kout) -> int {
-        using KeyT = std::remove_pointer_t<decltype(kin)>;
-        hipLaunchKernelGGL((morton_multi_kernel<KeyT>), dim3((unsigned)ceil_div(S_max, BLK), nb, ns), dim3(BLK), 0, st, m, kin, vals_in);
-        FFB6D_LAUNCH_CHECK();
-        if (const int rc = sort_segments(kin, kout, vals_in, vals_out, n, B * nsets, plan, ws + W.temp, W.temp_bytes, st, "knn_prepare_multi"))
-            return rc;
-        hipLaunchKernelGGL((gather_box_multi_kernel<KeyT>), dim3((unsigned)ceil_div(nt_max, BLK / 64), nb, ns), dim3(BLK), 0, st, m, kout,
-                           vals_out);
-        return FFB6D_OK;
-    };
-    const int rc = B * nsets <= MAX_SEG32 ? run(reinterpret_cast<uint32_t*>(keys_in), reinterpret_cast<uint32_t*>(keys_out))
-                                          : run(keys_in, keys_out);
-    if (rc) return rc;
-    hipLaunchKernelGGL(box2_multi_kernel, dim3((unsigned)ceil_div(nt2_max, BLK), nb, ns), dim3(BLK), 0, st, m);
-    hipLaunchKernelGGL(cell_table_multi_kernel, dim3(NCELL / BLK, nb, ns), dim3(BLK), 0, st, m);
-    FFB6D_LAUNCH_CHECK();
-    return FFB6D_OK;
+    return prepare_sets("knn_prepare_multi", nsets, pts, npts, B, prepared, prepared_bytes, workspace, workspace_bytes, as_stream(stream));
 }
 
 int ffb6d_knn_search_prepared(const void* prep_support, const void* prep_query, const float* raw_query,
@@ -1033,118 +996,15 @@ int ffb6d_knn_search_prepared(const void* prep_support, const void* prep_query, 
     FFB6D_REQUIRE(prep_query || (K >= 2 && K <= 16),
                   "knn_search_prepared: raw (unprepared) queries are supported for 2 <= K <= 16 only");
     FFB6D_REQUIRE(idx64 || idx32 || dist, "knn_search_prepared: no output requested");
-    const Layout LS = layout(B, S), LQ = layout(B, Q);
-    const char* ps = static_cast<const char*>(prep_support);
-    const char* pq = static_cast<const char*>(prep_query);
-    const float4* spts = reinterpret_cast<const float4*>(ps + LS.pts_off);
-    const float4* boxes = reinterpret_cast<const float4*>(ps + LS.box_off);
-    const uint32_t* skeys = reinterpret_cast<const uint32_t*>(ps + LS.key_off);
-    const float* sframe = reinterpret_cast<const float*>(ps + LS.frame_off);
-    const uint32_t* scell = reinterpret_cast<const uint32_t*>(ps + LS.cell_off);
-    const float4* qpts = prep_query ? reinterpret_cast<const float4*>(pq + LQ.pts_off) : nullptr;
-    dim3 grid((unsigned)ceil_div(LQ.S_pad, BLK), (unsigned)B);
-    hipStream_t st = as_stream(stream);
-    const int Kp = pad_k(K);
-    FFB6D_REQUIRE(K <= 16 || prep_query, "knn_search_prepared: K > 16 needs prepared queries");
-    if (K >= 2 && K <= 16) {   // row-cooperative kernel: 16 lanes per query
-        const float4* boxes2 = reinterpret_cast<const float4*>(ps + LS.box2_off);
-        dim3 rgrid((unsigned)ceil_div(LQ.S_pad, BLK / 16), (unsigned)B);
-#define FFB6D_LAUNCH_ROW(KK)                                                                                  \
-    hipLaunchKernelGGL((knn_row16_kernel<KK>), rgrid, dim3(BLK), 0, st, spts, boxes, boxes2, sframe, skeys,    \
-                       (int)S, (int)LS.S_pad, (int)LS.nt, (int)LS.nt2, qpts, prep_query ? nullptr : raw_query, (int)Q,  \
-                       (int)LQ.S_pad, idx64, idx32, dist, K)
-        switch (Kp) {
-            case 2: FFB6D_LAUNCH_ROW(2); break;
-            case 4: FFB6D_LAUNCH_ROW(4); break;
-            case 8: FFB6D_LAUNCH_ROW(8); break;
-            default: FFB6D_LAUNCH_ROW(16); break;
-        }
-#undef FFB6D_LAUNCH_ROW
-        FFB6D_LAUNCH_CHECK();
-        return FFB6D_OK;
-    }
-    const size_t lds = (size_t)(BLK / 64) * PT * sizeof(float4) + (Kp > 1 ? (size_t)QCAP * BLK * sizeof(uint2) : 0);
-#define FFB6D_LAUNCH_PRUNED(KK)                                                                              \
-    hipLaunchKernelGGL((knn_pruned_kernel<KK>), grid, dim3(BLK), lds, st, spts, boxes, skeys, sframe, scell, (int)S, \
-                       (int)LS.S_pad, (int)LS.nt, qpts, (int)Q, (int)LQ.S_pad, idx64, idx32, dist, K)
-    switch (Kp) {
-        case 1: FFB6D_LAUNCH_PRUNED(1); break;
-        case 2: FFB6D_LAUNCH_PRUNED(2); break;
-        case 4: FFB6D_LAUNCH_PRUNED(4); break;
-        case 8: FFB6D_LAUNCH_PRUNED(8); break;
-        case 16: FFB6D_LAUNCH_PRUNED(16); break;
-        case 32: FFB6D_LAUNCH_PRUNED(32); break;
-        default: return set_error(FFB6D_ERR_ARG, "knn_search_prepared: unsupported K=%d", K);
-    }
-#undef FFB6D_LAUNCH_PRUNED
-    FFB6D_LAUNCH_CHECK();
-    return FFB6D_OK;
+    const ffb6d_knn_search_t one = {prep_support, prep_query, nullptr, raw_query, S, Q, K, idx64, idx32, dist};
+    const int which = 0;
+    return knn_search_multi_prepared(&one, &which, 1, B, as_stream(stream));
 }
 
-}  // extern "C"
-
-namespace ffb6d {
-// Searches of `s` (indices `which`, all routed to the Morton-ordered kernels) in as few launches as kernels: one per padded K
-// of the 16-lane row kernel, one for K = 1.  Called by ffb6d_knn_search_multi (csrc/knn.hip).
-int knn_search_multi_prepared(const ffb6d_knn_search_t* s, const int* which, int n, int64_t B, hipStream_t st)
-{
-    const int kps[5] = {1, 2, 4, 8, 16};
-    for (int kp : kps) {
-        MultiPruned m;
-        m.n = 0;
-        int blocks = 0;
-        auto flush = [&]() -> int {
-            if (m.n == 0) return FFB6D_OK;
-            const size_t lds = (size_t)(BLK / 64) * PT * sizeof(float4);
-            switch (kp) {
-                case 1: hipLaunchKernelGGL((knn_pruned_multi_kernel<1>), dim3((unsigned)blocks), dim3(BLK), lds, st, m); break;
-                case 2: hipLaunchKernelGGL((knn_row16_multi_kernel<2>), dim3((unsigned)blocks), dim3(BLK), 0, st, m); break;
-                case 4: hipLaunchKernelGGL((knn_row16_multi_kernel<4>), dim3((unsigned)blocks), dim3(BLK), 0, st, m); break;
-                case 8: hipLaunchKernelGGL((knn_row16_multi_kernel<8>), dim3((unsigned)blocks), dim3(BLK), 0, st, m); break;
-                default: hipLaunchKernelGGL((knn_row16_multi_kernel<16>), dim3((unsigned)blocks), dim3(BLK), 0, st, m); break;
-            }
-            FFB6D_LAUNCH_CHECK();
-            m.n = 0;
-            blocks = 0;
-            return FFB6D_OK;
-        };
-        for (int w = 0; w < n; ++w) {
-            const ffb6d_knn_search_t& q = s[which[w]];
-            if (pad_k(q.K) != kp) continue;
-            FFB6D_REQUIRE(q.prep_support && (q.prep_query || (q.query && q.K >= 2)), "knn_search_multi: search %d needs a prepared support "
-                          "and prepared (K = 1) or raw (K >= 2) queries", which[w]);
-            const Layout LS = layout(B, q.S), LQ = layout(B, q.Q);
-            const char* ps = static_cast<const char*>(q.prep_support);
-            const char* pq = static_cast<const char*>(q.prep_query);
-            PrunedArgs& a = m.a[m.n];
-            a.spts = reinterpret_cast<const float4*>(ps + LS.pts_off);
-            a.boxes = reinterpret_cast<const float4*>(ps + LS.box_off);
-            a.boxes2 = reinterpret_cast<const float4*>(ps + LS.box2_off);
-            a.skeys = reinterpret_cast<const uint32_t*>(ps + LS.key_off);
-            a.sframe = reinterpret_cast<const float*>(ps + LS.frame_off);
-            a.scell = reinterpret_cast<const uint32_t*>(ps + LS.cell_off);
-            a.qpts = pq ? reinterpret_cast<const float4*>(pq + LQ.pts_off) : nullptr;
-            a.qraw = pq ? nullptr : q.query;
-            a.idx64 = q.idx64; a.idx32 = q.idx32; a.dist = q.dist;
-            a.S = (int)q.S; a.S_pad = (int)LS.S_pad; a.nt = (int)LS.nt; a.nt2 = (int)LS.nt2;
-            a.Q = (int)q.Q; a.Q_pad = (int)LQ.S_pad; a.Kout = q.K;
-            a.gx = (int)ceil_div(LQ.S_pad, kp == 1 ? BLK : BLK / 16);
-            a.blk0 = blocks;
-            blocks += a.gx * (int)B;
-            if (++m.n == MAX_SEARCHES) {
-                const int rc = flush();
-                if (rc != FFB6D_OK) return rc;
-            }
-        }
-        const int rc = flush();
-        if (rc != FFB6D_OK) return rc;
-    }
-    return FFB6D_OK;
-}
-}  // namespace ffb6d
-
-extern "C" int ffb6d_knn_set_pair_counter(unsigned long long* device_counter)
+int ffb6d_knn_set_pair_counter(unsigned long long* device_counter)
 {
     FFB6D_HIP_TRY(hipMemcpyToSymbol(HIP_SYMBOL(ffb6d::g_pair_counter), &device_counter, sizeof(device_counter)));
     return FFB6D_OK;
 }
+
+}  // extern "C"

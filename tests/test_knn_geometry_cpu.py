@@ -117,6 +117,10 @@ def test_seam_cases_on_the_emulator(emu, name, K, S):
     ("lattice_mid", 1025, 33, 1, 1),          # the nearest neighbour itself is a 2-, 4- or 8-way tie
     ("lattice_mid", 513, 33, 1, 2),
     ("lattice_mid", 1025, 33, 16, 1),
+    # a single call is one entry in the table of a batched kernel: query block (local % gx) and frame (local / gx) both count
+    ("origin_heavy", 513, 257, 1, 2),         # wave kernel, two query blocks, two frames
+    ("lattice", 513, 257, 32, 2),             # wave kernel with a register list and its LDS queue, two frames
+    ("lattice", 500, 257, 16, 2),             # scan, two blocks, two frames
 ])
 def test_more_geometries_on_the_emulator(emu, name, S, Q, K, B):
     _, sup, qry = knn_cases.build(name, S, Q, B=B)

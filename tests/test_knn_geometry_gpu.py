@@ -40,6 +40,8 @@ def _cases():
     c += [("origin_heavy", 5000, 2000, K, 1, torch.int64) for K in (1, 16, 32)]      # the largest case
     c += [("lattice", 4096, 2000, 16, 1, torch.int64)]
     c += [("line_lattice", S, Q, 1, 1, torch.int64) for S in (513, 1025) for Q in (64, 257)]      # see tests/test_knn_geometry_cpu.py
+    c += [("origin_heavy", 500, 1025, 1, 2, torch.int64)]     # scan with 4 queries per lane: two blocks, two frames in one flattened grid
+    c += [("lattice", 500, 257, 32, 2, torch.int32)]
     seen, out = set(), []
     for x in c:
         if x[:5] not in seen:
@@ -102,6 +104,18 @@ def test_every_entry_point_equals_the_single_call(device, name):
     for dt in (torch.int64, torch.int32):
         for got, ref, (_, _, K) in zip(nn.search_many(searches, dtype=dt), want, searches):
             assert got.dtype == dt and torch.equal(got, ref.to(dt)), (name, K, dt)
+
+
+def test_more_than_256_segments_sort_on_64_bit_keys(device):
+    """257 frames: a prepare with more than 256 (set, frame) segments carries the segment number above bit 32 of the sort key
+    and sorts with rocPRIM instead of the segmented 32-bit sort -- single calls and sets prepared together alike"""
+    _, sup, qry = knn_cases.build("two_clusters", 513, 17, B=257)
+    s, q = torch.from_numpy(sup).to(device), torch.from_numpy(qry).to(device)
+    for K in (1, 16):
+        _check(f"two_clusters S=513 Q=17 K={K} B=257", sup, qry, K, *_run(device, sup, qry, K))
+    for m, p in zip(nn.prepare_many([s, q]), (s, q)):
+        one = nn.PreparedPoints(p)
+        assert m.S == one.S and torch.equal(m.blob[:-256], one.blob[:-256])     # (the last < 256 bytes are alignment padding)
 
 
 # (c) ------------------------------------------------------------------------------------------------------------------------

@@ -38,7 +38,7 @@ def test_device_knn_matches_reference_goldens(device):
     (1, 12288, 12288, 16),   # self-KNN, level 0
     (2, 3072, 12288, 1),     # up-sampling 1-NN
     (1, 19200, 3072, 16),    # r2p: image grid support
-    (2, 76800, 768, 16),     # split-S path (few queries, big grid)
+    (2, 76800, 768, 16),     # few queries, big grid: the 16-lane row kernel on the Morton-ordered grid
     (1, 768, 76800, 1),      # p2r: many queries
     (3, 48, 192, 1), (3, 192, 192, 16), (1, 16, 5, 16), (1, 1000, 1, 16), (1, 1023, 257, 7),
     (1, 2049, 255, 32), (4, 4800, 48, 16), (1, 5000, 300, 2),
