@@ -462,6 +462,14 @@ mlp_pm_stream_kernel(const PmParams p)
 //   multiply (a second accumulator set drained during the next tile needs the 96 staging registers back: LDS-DMA operand loads) --
 //   a different kernel, not a variant of this one.
 // ---------------------------------------------------------------------------------------------------------------
+// the weight matrix of point tile pt (PmParams::rows_per_w: batched weights; one matrix when it is 0).  pt is wave-uniform.
+template <int SZ>
+__device__ __forceinline__ const void* batched_w(const PmParams& p, int pt)
+{
+    const size_t which = p.rows_per_w ? (size_t)(pt * 128 / p.rows_per_w) : 0;
+    return static_cast<const unsigned char*>(p.w) + which * (size_t)p.w_stride * SZ;
+}
+
 template <typename T>
 __global__ void __launch_bounds__(BLK, 2)            // two workgroups per CU (LDS allows two): at most 256 registers per lane
 mlp_pm_lds_kernel(const PmParams p)
@@ -488,7 +496,7 @@ mlp_pm_lds_kernel(const PmParams p)
     const int kb1 = p.k1 * SZ, kbt = K * SZ;          // row bytes of x1, of [x1 | x2] (= of a W row)
     const int nstage = (kbt + CB - 1) / CB;
 
-    const __amdgpu_buffer_rsrc_t rs_w = make_rsrc(p.w, (unsigned)p.cout * (unsigned)kbt);
+    const __amdgpu_buffer_rsrc_t rs_w = make_rsrc(batched_w<SZ>(p, pt), (unsigned)p.cout * (unsigned)kbt);
     const unsigned x1_rows = p.xidx ? (unsigned)(p.rows / p.P) * (unsigned)p.px : (unsigned)p.rows;
     const __amdgpu_buffer_rsrc_t rs_x1 = make_rsrc(p.x1, span_bytes(x1_rows, p.ld1, p.k1, SZ));
     const __amdgpu_buffer_rsrc_t rs_x2 = make_rsrc(p.x2 ? p.x2 : p.x1, p.x2 ? span_bytes((unsigned)p.rows, p.ld2, p.k2, SZ) : 0u);
@@ -721,7 +729,8 @@ mlp_pm_seq_kernel(const PmParams p)
     const int nstage = kbt / CB;                      // >= 4 (launcher)
     const int total = ntile * nstage;                 // steps of this workgroup
 
-    const __amdgpu_buffer_rsrc_t rs_w = make_rsrc(p.w, (unsigned)p.cout * (unsigned)kbt);
+    // (batched weights: the launcher sends whole-point-tile groups only, never LIN -- the matrix is the workgroup's for its whole sequence)
+    const __amdgpu_buffer_rsrc_t rs_w = make_rsrc(batched_w<SZ>(p, pt), (unsigned)p.cout * (unsigned)kbt);
     const unsigned x1_rows = p.xidx ? (unsigned)(p.rows / p.P) * (unsigned)p.px : (unsigned)p.rows;
     const __amdgpu_buffer_rsrc_t rs_x1 = make_rsrc(p.x1, span_bytes(x1_rows, p.ld1, p.k1, SZ));
     const __amdgpu_buffer_rsrc_t rs_x2 = make_rsrc(TWO ? p.x2 : p.x1, TWO ? span_bytes((unsigned)p.rows, p.ld2, p.k2, SZ) : 0u);
@@ -1431,7 +1440,9 @@ extern "C" int ffb6d_mlp_pm_choice(int64_t rows, int64_t cout, int64_t k1, int64
 static int g_seq_lin = 0;
 extern "C" void ffb6d_mlp_pm_set_seq_lin(int on) { g_seq_lin = on; }
 
-extern "C" int ffb6d_mlp_pm_seq_plan(int64_t rows, int64_t cout)
+// groups_only: the round-5 whole-point-tile plan whatever ffb6d_mlp_pm_set_seq_lin says (batched weights: a sequence must stay inside
+// one point tile, whose weight matrix it multiplies)
+static int seq_plan(int64_t rows, int64_t cout, bool groups_only)
 {
     // Measured on the long-row launches of the bench step (profiles/r05_seq_gemm_sweep.txt; sweep over T, the regions' sizes):
     //   * T ~ half the number of rounds the tiles make over the chip's 512 workgroup slots, at least 2, at most the channel tiles, nudged
@@ -1440,7 +1451,7 @@ extern "C" int ffb6d_mlp_pm_seq_plan(int64_t rows, int64_t cout)
     //     tiles (with 2-3 channel tiles per point tile the tail of single tiles measured slower than none).
     const int64_t n_pt = ceil_div(rows, 128), n_ct = ceil_div(cout, 128), tiles = n_pt * n_ct;
     if (n_ct < 2 || tiles < 1024) return 1;
-    if (g_seq_lin && n_ct <= 8) {
+    if (g_seq_lin && n_ct <= 8 && !groups_only) {
         // round 6: balanced contiguous sequences (they may run from one point tile into the next).  Sequences of ~3 tiles, at least two
         // per workgroup slot: the dispatcher keeps something to hand out (one resident sequence per slot lost inside the
         // three-stream step in round 4), the slots drain together (lengths differ by one, the longer ones first)
@@ -1458,6 +1469,8 @@ extern "C" int ffb6d_mlp_pm_seq_plan(int64_t rows, int64_t cout)
     const int64_t b_tiles = tb > 1 ? 512 : 0, c_tiles = n_ct >= 4 ? 512 : 0;
     return (int)(ta | tb << 4 | (b_tiles / 16) << 8 | (c_tiles / 16) << 16);
 }
+
+extern "C" int ffb6d_mlp_pm_seq_plan(int64_t rows, int64_t cout) { return seq_plan(rows, cout, false); }
 
 #define FFB6D_MLP_PM_ARGS                                                                                                    \
     bias, x1, k1, ld1, x1_idx, x1_rows_per_frame, x2, k2, ld2, y, ldy, y_idx, y_rows_per_frame, idx_bits, rows_per_frame, out, \
@@ -1491,4 +1504,46 @@ extern "C" int ffb6d_att_pool_pm_bf16(const void* w_fc, const void* f, int64_t c
                                       ffb6d_stream_t stream)
 {
     return att_pool_pm_impl<__bf16>(w_fc, f, c1, ldf, nei, idx_bits, g, c2, ldg, out, ldo, B, N, K, stream);
+}
+
+// Batched weights on the long-row fp32 forms: rows [i * rows_per_w, (i + 1) * rows_per_w) multiply the matrix w + i * w_stride.  One launch
+// for all matrices (the 16 planes of a Winograd-transformed convolution, csrc/winograd.h: 16 launches of a sixteenth of the tiles each
+// would leave the chip's 512 workgroup slots partly empty 16 times).  No bias, no epilogue rows, no activation, no gathered operand.
+extern "C" int ffb6d_mlp_pm_batched_f32(const float* w, int64_t w_stride, int64_t rows_per_w, const float* x, int64_t k, int64_t ld,
+                                        float* out, int64_t ldo, int64_t rows, int64_t cout, int tile_hint, ffb6d_stream_t stream)
+{
+    FFB6D_REQUIRE(rows >= 0 && cout >= 1 && k >= 1, "mlp_pm_batched: bad shape");
+    FFB6D_REQUIRE(rows_per_w >= 128 && rows_per_w % 128 == 0 && rows_per_w < (1LL << 31), "mlp_pm_batched: rows_per_w must be a positive multiple of 128 (got %lld): "
+                  "a point tile multiplies one matrix", (long long)rows_per_w);
+    if (rows == 0) return FFB6D_OK;
+    FFB6D_REQUIRE(w && x && out, "mlp_pm_batched: null pointer");
+    FFB6D_REQUIRE(ld >= k && ldo >= cout && w_stride >= cout * k, "mlp_pm_batched: stride smaller than the row / the matrix");
+    const int form = tile_hint <= 0 ? 8 : (tile_hint & 255);
+    int plan = tile_hint > 0 ? tile_hint >> 8 : 0;
+    FFB6D_REQUIRE(form == 7 || form == 8, "mlp_pm_batched: tile_hint must be 0, 7 (LDS-tiled form) or 8 + 256 * plan (tile-sequence form)");
+    FFB6D_REQUIRE(!(form == 8 && plan > 0 && seq_plan_is_lin(plan)), "mlp_pm_batched: a balanced-sequence (LIN) plan may run from one point "
+                  "tile into the next, across a weight boundary");
+    const int64_t n_w = ceil_div(rows, rows_per_w);
+    FFB6D_REQUIRE((rows + 256) * ld * 4 < (1LL << 31) && (rows + 256) * ldo * 4 < (1LL << 31) && (cout + 128) * k * 4 < (1LL << 31) &&
+                  n_w * w_stride * 4 < (1LL << 31), "mlp_pm_batched: operand larger than the 2 GiB buffer addressing of one launch");
+    PmParams p;
+    p.w = w; p.bias = nullptr; p.x1 = x; p.xidx = nullptr; p.x2 = nullptr; p.y = nullptr; p.gidx = nullptr; p.out = out;
+    p.rows = (int)rows; p.cout = (int)cout; p.k1 = (int)k; p.k2 = 0; p.ld1 = (int)ld; p.ld2 = 4; p.ldy = 0; p.ldo = (int)ldo;
+    p.P = (int)rows; p.py = 0; p.px = 0; p.act = 0; p.idx64 = 0;
+    p.rows_per_w = (int)rows_per_w; p.w_stride = (int)w_stride;
+    // what the tile-sequence form accepts (seq_form_ok) -- asked of the LDS-tiled form too, so that both forms take the same launches
+    FFB6D_REQUIRE((ld * 4) % 16 == 0 && (w_stride * 4) % 16 == 0 &&
+                  ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(w)) & 15) == 0 && seq_form_ok(p, k, 0),
+                  "mlp_pm_batched: needs fp32 rows of whole 128-byte segments, K >= 128, cout %% 4 == 0 and 16-byte aligned rows");
+    hipStream_t st = as_stream(stream);
+    bool ok;
+    if (form == 7) {
+        ok = launch_lds<float>(p, st);
+    } else {
+        if (plan <= 0) plan = seq_plan(rows, cout, true);
+        ok = launch_seq<false>(p, plan, st);
+    }
+    if (!ok) return set_error(FFB6D_ERR_HIP, "mlp_pm_batched: hipFuncSetAttribute(MaxDynamicSharedMemorySize) failed");
+    FFB6D_LAUNCH_CHECK();
+    return FFB6D_OK;
 }

@@ -33,6 +33,9 @@ struct PmParams {
     int tpg, tpg_b, pt_b, pt_c, wg_b, wg_c;
     // ... or (round 6) lin_wg > 0: every XCD's tile list cut into lin_wg balanced contiguous sequences (mlp_pm_seq_kernel: LIN)
     int lin_wg = 0;
+    // batched weights (LDS-tiled and tile-sequence forms): point tile t multiplies the matrix at w + (t * 128 / rows_per_w) * w_stride
+    // elements; rows_per_w (a multiple of 128: a point tile never straddles two matrices) = 0: one matrix for every row
+    int rows_per_w = 0, w_stride = 0;
 };
 
 // epilogue shared by the GEMM kernels: bias, gathered / added row of Y, activation or log-softmax, store

@@ -17,9 +17,11 @@
 // 16-byte units of 4 or 8 channels per lane, arithmetic in fp32, stores rounded to nearest even).
 #include <cfloat>
 
+#include "affine_act.h"
 #include "common.h"
 #include "ffb6d_ops.h"
 #include "row_unit.h"
+#include "winograd.h"
 
 namespace ffb6d {
 namespace {
@@ -28,17 +30,6 @@ constexpr int BLK = 256;
 
 // a 16-byte unit of a row: VL consecutive channels, held as fp32 in registers (csrc/row_unit.h)
 template <typename T> using Unit = RowUnit<T>;
-// fp32 per-channel parameters (BatchNorm scale / shift) of a unit's VL channels
-template <int VL>
-__device__ __forceinline__ void load_params(const float* p, int unit, float (&out)[VL])
-{
-#pragma unroll
-    for (int i = 0; i < VL; i += 4) {
-        const float4 f = *reinterpret_cast<const float4*>(p + (size_t)unit * VL + i);
-        out[i] = f.x; out[i + 1] = f.y; out[i + 2] = f.z; out[i + 3] = f.w;
-    }
-}
-
 __device__ __forceinline__ float max_nan(float m, float v)   // torch.max semantics: NaN propagates
 {
     return (v > m || v != v) ? v : m;
@@ -166,23 +157,16 @@ affine_act_pm_kernel(const void* __restrict__ x, const float* __restrict__ scale
     load_params<U::VL>(scale, c, s);
     load_params<U::VL>(shift, c, b);
     U v = U::load(x, t);
-#pragma unroll
-    for (int e = 0; e < U::VL; ++e) v.v[e] = v.v[e] * s[e] + b[e];
+    U r;
+    float rs[U::VL], rb[U::VL];
     if (res) {
-        const U r = U::load(res, t);
+        r = U::load(res, t);
         if (rscale) {
-            float rs[U::VL], rb[U::VL];
             load_params<U::VL>(rscale, c, rs);
             load_params<U::VL>(rshift, c, rb);
-#pragma unroll
-            for (int e = 0; e < U::VL; ++e) v.v[e] += r.v[e] * rs[e] + rb[e];
-        } else {
-#pragma unroll
-            for (int e = 0; e < U::VL; ++e) v.v[e] += r.v[e];
         }
     }
-#pragma unroll
-    for (int e = 0; e < U::VL; ++e) v.v[e] = v.v[e] > 0.f ? v.v[e] : slope * v.v[e];     // exact PReLU for ANY learned slope (> 1, < 0)
+    affine_act_unit<U::VL>(v.v, s, b, res ? r.v : nullptr, rscale != nullptr, rs, rb, slope);
     v.store(out, t);
 }
 
@@ -616,6 +600,18 @@ int ffb6d_affine_act_pm(int dtype, const void* x, const float* scale, const floa
     })
     FFB6D_LAUNCH_CHECK();
     return FFB6D_OK;
+}
+
+int ffb6d_wino_input_f32(const float* x, float* v, int64_t B, int64_t H, int64_t W, int64_t C, int64_t Tp, ffb6d_stream_t stream)
+{
+    return wino::input_f32(x, v, B, H, W, C, Tp, stream);
+}
+
+int ffb6d_wino_output_f32(const float* m, const float* scale, const float* shift, const float* res, const float* rscale,
+                          const float* rshift, float* out, int64_t B, int64_t H, int64_t W, int64_t O, int64_t Tp, int act, float slope,
+                          ffb6d_stream_t stream)
+{
+    return wino::output_f32(m, scale, shift, res, rscale, rshift, out, B, H, W, O, Tp, act, slope, stream);
 }
 
 int ffb6d_affine_relu_maxpool_pm(int dtype, const void* x, const float* scale, const float* shift, void* out, int64_t B, int64_t IH,

@@ -20,7 +20,8 @@ Fusions (reference ops -> here), all inference only:
     choose gather + cat + head conv                       operand gather of the head GEMM
     final conv1x1 + LogSoftmax                            log-softmax epilogue of the GEMM
     pyramid pooling                                       W_x x + b + sum_i up_i((W_b,i W_i) pool_i(x))
-Dense 3x3 / 7x7 convolutions stay on MIOpen, fed channels_last tensors and weights.
+    conv3x3 (Cin >= 256) + BN (+ residual) + ReLU         Winograd F(2x2,3x3): transform, batched GEMM, transform + BN/ReLU (fp32)
+The other dense 3x3 / 7x7 convolutions stay on MIOpen, fed channels_last tensors and weights.
 """
 import torch
 import torch.nn.functional as F
@@ -259,14 +260,69 @@ def conv(x, c):
     return y if y.is_contiguous() else y.contiguous()
 
 
+# The wide stride-1 3x3 convolutions of the trunk (fp32, Cin >= TRUNK_WINOGRAD_MIN_CIN) as Winograd F(2x2,3x3): input transform ->
+# ONE batched tile-sequence GEMM over the 16 transformed planes (2.25x fewer multiplies than the direct form) -> output transform with the
+# BatchNorm / residual / ReLU pass of the block fused in (csrc/winograd.h).  False: MIOpen + affine_act_ for
+# those layers too.  Within HOT_TOL of the direct form (measured <= 1.8e-6 of range on outputs and stage taps), not equal bits; the
+# converted layers repeat their bits from run to run.  Measured (profiles/winograd_trunk_ab.json): step 20.05 -> 15.66 ms; with the
+# threshold at 512 17.2 ms -- the eleven 256-wide layers are worth 1.5 ms, so the threshold is 256 (the 64- and 128-wide layers: not built).
+TRUNK_WINOGRAD = True
+TRUNK_WINOGRAD_MIN_CIN = 256
+
+
+def wino_filter(w):
+    """U [16, O, Cin] = (G g G^T)[u, v] at plane 4u + v of a [O, Cin, 3, 3] filter: computed in float64, rounded once to float32"""
+    G = torch.tensor([[1, 0, 0], [.5, .5, .5], [.5, -.5, .5], [0, 0, 1]], dtype=torch.float64, device=w.device)
+    u = G @ w.detach().double() @ G.T                                                   # [O, Cin, 4, 4]
+    return u.permute(2, 3, 0, 1).reshape(16, w.shape[0], w.shape[1]).float().contiguous()
+
+
+def wino_weights(c):
+    """wino_filter of a convolution's weight, once per weight version (the weights are constant from call to call in deployment)"""
+    return cached(c, "wino", [c.weight], lambda: wino_filter(c.weight))
+
+
+def wino_ok(c, x):
+    """Does convolution `c` on the [B,H,W,C] map x take the Winograd path?  fp32, 3x3 / stride 1 / padding 1 / dilation 1 / one group / no
+    bias, Cin at the threshold or above, widths the batched GEMM accepts (rows of whole 128-byte segments, K >= 128), every buffer < 2 GiB."""
+    if not TRUNK_WINOGRAD or x.dtype != torch.float32 or c.weight.dtype != torch.float32:
+        return False
+    if (c.kernel_size, c.stride, c.padding, c.dilation, c.groups) != ((3, 3), (1, 1), (1, 1), (1, 1), 1) or c.bias is not None \
+            or c.padding_mode != "zeros":
+        return False
+    cout, cin = c.weight.shape[:2]
+    if cin < TRUNK_WINOGRAD_MIN_CIN or cin < 128 or cin % 32 or cout % 4:
+        return False
+    B, H, W, _ = x.shape
+    Tp = ops_pm.wino_tiles(B, H, W)[1]
+    lim = (1 << 31) - (1 << 20)
+    return 16 * (Tp + 256) * max(cin, cout) * 4 < lim and B * H * W * max(cin, cout) * 4 < lim and 16 * cout * cin * 4 < lim
+
+
+def conv_wino(x, c, scale, shift, residual=None, res_affine=None):
+    """relu(scale * conv3x3(x) + shift + residual term) of a [B,H,W,C] map by Winograd F(2x2,3x3); V and M come from the caching
+    allocator on the current stream and go back to it as soon as the next kernel is queued (the next layer reuses the blocks)."""
+    u = wino_weights(c)
+    v = ops_pm.wino_input(x if x.is_contiguous() else x.contiguous())
+    m = ops_pm.mlp_batched(v, u)
+    return ops_pm.wino_output(m, x.shape[:3], scale, shift, act=ops.ACT_RELU, residual=residual, res_affine=res_affine)
+
+
 def res_block(rb, x):
     """extractors.py:49-63 (BasicBlock): BN+ReLU and BN+residual(+BN of the projection)+ReLU as one pass each."""
-    y = ops_pm.affine_act_(conv(x, rb.conv1), *ops.bn_fold(rb.bn1), act=ops.ACT_RELU)
-    y = conv(y, rb.conv2)
+    if wino_ok(rb.conv1, x):
+        y = conv_wino(x, rb.conv1, *ops.bn_fold(rb.bn1))
+    else:
+        y = ops_pm.affine_act_(conv(x, rb.conv1), *ops.bn_fold(rb.bn1), act=ops.ACT_RELU)
+    wino2 = wino_ok(rb.conv2, y)
+    if not wino2:
+        y = conv(y, rb.conv2)
+    res, res_affine = x, None
     if rb.downsample is not None:
-        return ops_pm.affine_act_(y, *ops.bn_fold(rb.bn2), act=ops.ACT_RELU, residual=conv(x, rb.downsample[0]),
-                                  res_affine=ops.bn_fold(rb.downsample[1]))
-    return ops_pm.affine_act_(y, *ops.bn_fold(rb.bn2), act=ops.ACT_RELU, residual=x)
+        res, res_affine = conv(x, rb.downsample[0]), ops.bn_fold(rb.downsample[1])
+    if wino2:
+        return conv_wino(y, rb.conv2, *ops.bn_fold(rb.bn2), residual=res, res_affine=res_affine)
+    return ops_pm.affine_act_(y, *ops.bn_fold(rb.bn2), act=ops.ACT_RELU, residual=res, res_affine=res_affine)
 
 
 def pyramid_pooling(pp, x):

@@ -157,6 +157,28 @@ void ffb6d_mlp_pm_set_seq_lin(int on);
  * Identical results. */
 void ffb6d_mlp_pm_set_big_form(int on);
 
+/* Batched weights on the two long-row fp32 forms: out[r,:] = w_i x[r,:] with i = r / rows_per_w and w_i = w + i * w_stride floats, each
+ * [cout, k] -- one launch for all matrices (the 16 planes of a Winograd-transformed convolution).  rows_per_w must be a multiple of 128
+ * (a point tile multiplies ONE matrix); no bias, epilogue rows, activation or operand gather.  tile_hint: 0 = the tile-sequence form with
+ * the whole-point-tile plan of ffb6d_mlp_pm_seq_plan, 8 + 256 * plan = that form with an explicit plan (a balanced-sequence plan is
+ * refused: its sequences cross point tiles), 7 = the LDS-tiled form.  Needs what the tile-sequence form needs (k * 4 a multiple of 128,
+ * k >= 128, cout a multiple of 4, 16-byte aligned rows); anything else is an error, nothing is launched.  Each output row carries the
+ * bits ffb6d_mlp_pm_f32 gives for (w_i, its rows) alone. */
+int ffb6d_mlp_pm_batched_f32(const float* w, int64_t w_stride, int64_t rows_per_w, const float* x, int64_t k, int64_t ld, float* out,
+                             int64_t ldo, int64_t rows, int64_t cout, int tile_hint, ffb6d_stream_t stream);
+
+/* Winograd F(2x2,3x3) data transforms around that GEMM (csrc/winograd.h; 3x3 convolution, stride 1, padding 1, fp32).
+ * T = B * ceil(H/2) * ceil(W/2) tiles numbered (b, ty, tx); Tp >= T, a multiple of 128; plane xi = 4u + v = position (u, v) of the
+ * transformed 4 x 4 tile.  Every tensor must stay under 2 GiB (error otherwise).
+ * input:  x [B,H,W,C] -> v [16][Tp][C] = B^T d B of the 4 x 4 window at (2ty - 1, 2tx - 1), zeros outside the map; rows T..Tp-1 of a
+ *         plane are left unwritten.
+ * output: m [16][Tp][O] -> out [B,H,W,O] = act( scale * (A^T m A) + shift + (res ? (rscale ? rscale*res + rshift : res) : 0) ), the
+ *         arithmetic of ffb6d_affine_act_pm; res [B,H,W,O] must not alias out. */
+int ffb6d_wino_input_f32(const float* x, float* v, int64_t B, int64_t H, int64_t W, int64_t C, int64_t Tp, ffb6d_stream_t stream);
+int ffb6d_wino_output_f32(const float* m, const float* scale, const float* shift, const float* res, const float* rscale,
+                          const float* rshift, float* out, int64_t B, int64_t H, int64_t W, int64_t O, int64_t Tp, int act, float slope,
+                          ffb6d_stream_t stream);
+
 /* Att_pooling.forward up to the pooled tensor (RandLANet.py:243-248) with the neighbour gather fused in:
  * S[(n,k),:] = [ f[nei[n,k],:] | g[(n,k),:] ], out[n,m] = sum_k S[(n,k),m] * softmax_k((S w_fc^T)[(n,k),m]).
  * f [B*N, ldf] point rows (c1 channels), nei [B,N,16] indices inside the frame, g [B*N*16, ldg] pair rows (c2 channels),

@@ -1,0 +1,58 @@
+#!/usr/bin/env python3
+"""One wide trunk convolution (3x3, stride 1, BatchNorm + residual + ReLU) alone on the chip, direct against Winograd F(2x2,3x3):
+MIOpen + affine_act_ against input transform -> batched GEMM -> output transform (forward_pm.conv_wino), each stage timed by itself
+with device events.  Prints one JSON line per width: microseconds per launch, the GEMM's TFLOP/s and its share of the fp32 MFMA peak,
+each transform's GB/s by algorithmic bytes.
+argv: [B H W] (default 8 60 80: the trunk map of the benchmark) [reps]"""
+import json
+import os
+import sys
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import torch
+
+from ffb6d_amd import forward_pm, ops, ops_pm
+
+PEAK_TFLOPS = 157.3        # fp32 MFMA, MI355X
+dev = torch.device("cuda:0")
+B, H, W = (int(v) for v in sys.argv[1:4]) if len(sys.argv) > 3 else (8, 60, 80)
+reps = int(sys.argv[4]) if len(sys.argv) > 4 else 20
+torch.manual_seed(0)
+
+
+def timed(fn):
+    for _ in range(3):
+        fn()
+    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    a.record()
+    for _ in range(reps):
+        fn()
+    b.record()
+    torch.cuda.synchronize()
+    return 1e3 * a.elapsed_time(b) / reps
+
+
+with torch.no_grad():
+    for cin, cout in ((256, 256), (256, 512), (512, 512)):
+        conv = torch.nn.Conv2d(cin, cout, 3, 1, 1, bias=False).to(dev)
+        x, res = torch.randn(B, H, W, cin, device=dev), torch.randn(B, H, W, cout, device=dev)
+        scale, shift = torch.rand(cout, device=dev) + .5, torch.randn(cout, device=dev)
+        T, Tp = ops_pm.wino_tiles(B, H, W)
+        u = forward_pm.wino_weights(conv)
+        v, m = ops_pm.wino_input(x), torch.empty(16, Tp, cout, device=dev)
+        ops_pm.mlp_batched(v, u, out=m)
+        rec = {"shape": [B, H, W, cin, cout], "tiles": T,
+               "direct_conv_us": timed(lambda: forward_pm.conv(x, conv)),
+               "direct_conv_affine_us": timed(lambda: ops_pm.affine_act_(forward_pm.conv(x, conv), scale, shift, act=ops.ACT_RELU, residual=res)),
+               "wino_total_us": timed(lambda: forward_pm.conv_wino(x, conv, scale, shift, residual=res)),
+               "wino_input_us": timed(lambda: ops_pm.wino_input(x, out=v)),
+               "wino_gemm_us": timed(lambda: ops_pm.mlp_batched(v, u, out=m)),
+               "wino_gemm_lds_form_us": timed(lambda: ops_pm.mlp_batched(v, u, out=m, tile_hint=7)),
+               "wino_output_us": timed(lambda: ops_pm.wino_output(m, (B, H, W), scale, shift, act=ops.ACT_RELU, residual=res))}
+        px = B * H * W
+        rec["wino_gemm_tflops"] = 2.0 * 16 * T * cin * cout / rec["wino_gemm_us"] * 1e-6
+        rec["wino_gemm_frac_of_fp32_mfma_peak"] = rec["wino_gemm_tflops"] / PEAK_TFLOPS
+        rec["wino_input_GBps"] = 4.0 * (px * cin + 16 * T * cin) / rec["wino_input_us"] * 1e-3
+        rec["wino_output_GBps"] = 4.0 * (16 * T * cout + 2 * px * cout) / rec["wino_output_us"] * 1e-3
+        rec["direct_conv_tflops"] = 2.0 * 9 * px * cin * cout / rec["direct_conv_us"] * 1e-6
+        print(json.dumps({k: (round(v, 3) if isinstance(v, float) else v) for k, v in rec.items()}), flush=True)
