@@ -614,6 +614,18 @@ int ffb6d_wino_output_f32(const float* m, const float* scale, const float* shift
     return wino::output_f32(m, scale, shift, res, rscale, rshift, out, B, H, W, O, Tp, act, slope, stream);
 }
 
+int ffb6d_wino4_input_f32(const float* x, float* v, int64_t B, int64_t H, int64_t W, int64_t C, int64_t Tp, ffb6d_stream_t stream)
+{
+    return wino::input4_f32(x, v, B, H, W, C, Tp, stream);
+}
+
+int ffb6d_wino4_output_f32(const float* m, const float* scale, const float* shift, const float* res, const float* rscale,
+                           const float* rshift, float* out, int64_t B, int64_t H, int64_t W, int64_t O, int64_t Tp, int act, float slope,
+                           ffb6d_stream_t stream)
+{
+    return wino::output4_f32(m, scale, shift, res, rscale, rshift, out, B, H, W, O, Tp, act, slope, stream);
+}
+
 int ffb6d_affine_relu_maxpool_pm(int dtype, const void* x, const float* scale, const float* shift, void* out, int64_t B, int64_t IH,
                                  int64_t IW, int64_t C, ffb6d_stream_t stream)
 {

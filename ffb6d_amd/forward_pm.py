@@ -282,9 +282,40 @@ def wino_weights(c):
     return cached(c, "wino", [c.weight], lambda: wino_filter(c.weight))
 
 
-def wino_ok(c, x):
+# F(4x4,3x3) on the points 0, 1, -1, 2, -1/2 for the same layers where it is the cheaper variant: 36 planes of ceil(H/4) ceil(W/4) tiles
+# against 16 planes of ceil(H/2) ceil(W/2), both padded to the GEMM's 128-row point tile -- 0.57x the GEMM rows and 2.25x instead of 4x
+# the map in V and M on the benchmark's 8 x 60 x 80 trunk map (wino_variant).  False: F(2x2) everywhere.  Within
+# HOT_TOL of F(2x2) (measured <= 2.0e-6 of range).  Measured (profiles/winograd4_trunk_ab.json): step 15.65 -> 12.99 ms.
+TRUNK_WINOGRAD_F4 = True
+
+
+def wino4_filter(w):
+    """U [36, O, Cin] = (G g G^T)[u, v] at plane 6u + v of a [O, Cin, 3, 3] filter: computed in float64, rounded once to float32.  G
+    carries the inverse of the integer scale of B^T's rows (csrc/winograd.h)."""
+    G = torch.tensor([[1 / 2, 0, 0], [-1 / 6, -1 / 6, -1 / 6], [1 / 6, -1 / 6, 1 / 6], [1 / 30, 1 / 15, 2 / 15],
+                      [-16 / 15, 8 / 15, -4 / 15], [0, 0, 1 / 2]], dtype=torch.float64, device=w.device)
+    u = G @ w.detach().double() @ G.T                                                   # [O, Cin, 6, 6]
+    return u.permute(2, 3, 0, 1).reshape(36, w.shape[0], w.shape[1]).float().contiguous()
+
+
+def wino4_weights(c):
+    """wino4_filter of a convolution's weight, once per weight version"""
+    return cached(c, "wino4", [c.weight], lambda: wino4_filter(c.weight))
+
+
+def wino_variant(B, H, W):
+    """Output tile edge of the cheaper Winograd variant on a [B,H,W,.] map: 4 iff its GEMM has fewer rows, 36 Tp4 < 16 Tp2 with both
+    tile counts padded to 128 (transform traffic follows the same products); a tie stays with F(2x2), and so does everything when
+    TRUNK_WINOGRAD_F4 is off.  Small maps: the padding makes F(4x4) the dearer one."""
+    if not TRUNK_WINOGRAD_F4:
+        return 2
+    return 4 if 36 * ops_pm.wino4_tiles(B, H, W)[1] < 16 * ops_pm.wino_tiles(B, H, W)[1] else 2
+
+
+def wino_ok(c, x, m=None):
     """Does convolution `c` on the [B,H,W,C] map x take the Winograd path?  fp32, 3x3 / stride 1 / padding 1 / dilation 1 / one group / no
-    bias, Cin at the threshold or above, widths the batched GEMM accepts (rows of whole 128-byte segments, K >= 128), every buffer < 2 GiB."""
+    bias, Cin at the threshold or above, widths the batched GEMM accepts (rows of whole 128-byte segments, K >= 128), every buffer of
+    the variant it would take (m = 2 or 4; None: wino_variant) < 2 GiB."""
     if not TRUNK_WINOGRAD or x.dtype != torch.float32 or c.weight.dtype != torch.float32:
         return False
     if (c.kernel_size, c.stride, c.padding, c.dilation, c.groups) != ((3, 3), (1, 1), (1, 1), (1, 1), 1) or c.bias is not None \
@@ -294,18 +325,29 @@ def wino_ok(c, x):
     if cin < TRUNK_WINOGRAD_MIN_CIN or cin < 128 or cin % 32 or cout % 4:
         return False
     B, H, W, _ = x.shape
-    Tp = ops_pm.wino_tiles(B, H, W)[1]
+    if m is None:
+        m = wino_variant(B, H, W)
+    planes, Tp = (m + 2) ** 2, (ops_pm.wino4_tiles if m == 4 else ops_pm.wino_tiles)(B, H, W)[1]
     lim = (1 << 31) - (1 << 20)
-    return 16 * (Tp + 256) * max(cin, cout) * 4 < lim and B * H * W * max(cin, cout) * 4 < lim and 16 * cout * cin * 4 < lim
+    return planes * (Tp + 256) * max(cin, cout) * 4 < lim and B * H * W * max(cin, cout) * 4 < lim and planes * cout * cin * 4 < lim
 
 
-def conv_wino(x, c, scale, shift, residual=None, res_affine=None):
-    """relu(scale * conv3x3(x) + shift + residual term) of a [B,H,W,C] map by Winograd F(2x2,3x3); V and M come from the caching
-    allocator on the current stream and go back to it as soon as the next kernel is queued (the next layer reuses the blocks)."""
+def conv_wino(x, c, scale, shift, residual=None, res_affine=None, m=None):
+    """relu(scale * conv3x3(x) + shift + residual term) of a [B,H,W,C] map by Winograd F(m x m,3x3), m = 2 or 4 (None: wino_variant,
+    the cheaper one on this map); V and M come from the caching allocator on the current stream and go back to it as soon as the
+    next kernel is queued (the next layer reuses the blocks)."""
+    if m is None:
+        m = wino_variant(*x.shape[:3])
+    x = x if x.is_contiguous() else x.contiguous()
+    if m == 4:
+        mm = ops_pm.mlp_batched(ops_pm.wino4_input(x), wino4_weights(c))
+        return ops_pm.wino4_output(mm, x.shape[:3], scale, shift, act=ops.ACT_RELU, residual=residual, res_affine=res_affine)
+    if m != 2:
+        raise ValueError(f"conv_wino: m must be 2, 4 or None, got {m}")
     u = wino_weights(c)
-    v = ops_pm.wino_input(x if x.is_contiguous() else x.contiguous())
-    m = ops_pm.mlp_batched(v, u)
-    return ops_pm.wino_output(m, x.shape[:3], scale, shift, act=ops.ACT_RELU, residual=residual, res_affine=res_affine)
+    v = ops_pm.wino_input(x)
+    mm = ops_pm.mlp_batched(v, u)
+    return ops_pm.wino_output(mm, x.shape[:3], scale, shift, act=ops.ACT_RELU, residual=residual, res_affine=res_affine)
 
 
 def res_block(rb, x):

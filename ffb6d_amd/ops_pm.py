@@ -138,7 +138,7 @@ def mlp(x1, w, bias=None, act=ACT_NONE, x2=None, add=None, gather=None, x1_gathe
 
 def mlp_batched(x, w, out=None, tile_hint=0):
     """One launch for a stack of GEMMs that share their shape: x [G, R, K], w [G, Cout, K] -> out [G, R, Cout], out[g] = x[g] w[g]^T
-    (csrc/mlp_pm.hip: ffb6d_mlp_pm_batched_f32 -- the 16 planes of a Winograd-transformed convolution).  fp32, R a multiple of 128
+    (csrc/mlp_pm.hip: ffb6d_mlp_pm_batched_f32 -- the 16 or 36 planes of a Winograd-transformed convolution).  fp32, R a multiple of 128
     (a 128-row tile multiplies one matrix), no bias / activation.  tile_hint 0 = the tile-sequence form (the LDS-tiled form when
     MLP_SEQ_FORM is off), 7 / 8 + 256 * plan select explicitly.  Every out[g] carries the bits of mlp(x[g], w[g]) in the same form."""
     _need_gpu(x, w)
@@ -212,6 +212,58 @@ def wino_output(m, shape, scale, shift, act=ACT_NONE, slope=0.0, residual=None, 
                                        rs.data_ptr() if rs is not None else None, rb.data_ptr() if rb is not None else None,
                                        out.data_ptr(), B, H, W, O, Tp, int(act), float(slope), _stream(m))
     _lib.check(rc, "ffb6d_wino_output_f32")
+    return out
+
+
+def wino4_tiles(B, H, W):
+    """(T, Tp): tiles of Winograd F(4x4,3x3) on a [B,H,W,.] map and their count rounded up to the GEMM's 128-row point tile"""
+    T = B * ((H + 3) // 4) * ((W + 3) // 4)
+    return T, -(-T // 128) * 128
+
+
+def wino4_input(x, out=None):
+    """Input transform of Winograd F(4x4,3x3) (csrc/winograd.h): x [B,H,W,C] fp32 -> V [36,Tp,C], plane 6u+v = element (u,v) of
+    B^T d B over the 6 x 6 windows at (4ty-1, 4tx-1) (zeros outside the map).  Rows T..Tp-1 of every plane are left unwritten."""
+    _need_gpu(x)
+    lib = _lib.load()
+    if x.dtype != torch.float32 or x.dim() != 4 or not x.is_contiguous():
+        raise ValueError("wino4_input needs a contiguous float32 [B,H,W,C] map")
+    B, H, W, C = x.shape
+    T, Tp = wino4_tiles(B, H, W)
+    if out is None:
+        out = torch.empty(36, Tp, C, dtype=torch.float32, device=x.device)
+    if out.shape != (36, Tp, C) or not out.is_contiguous() or out.dtype != torch.float32:
+        raise ValueError(f"out must be contiguous float32 [36, {Tp}, {C}]")
+    with torch.cuda.device(x.device), _lib.traced("wino4_input", 4 * (x.numel() + 36 * T * C), (C, T)):
+        rc = lib.ffb6d_wino4_input_f32(x.data_ptr(), out.data_ptr(), B, H, W, C, Tp, _stream(x))
+    _lib.check(rc, "ffb6d_wino4_input_f32")
+    return out
+
+
+def wino4_output(m, shape, scale, shift, act=ACT_NONE, slope=0.0, residual=None, res_affine=None):
+    """Output transform of Winograd F(4x4,3x3) with the BatchNorm / residual / activation glue of affine_act_ applied on the way out
+    (csrc/winograd.h): m [36,Tp,O] fp32, shape = (B,H,W) -> [B,H,W,O] = act(scale * (A^T m A) + shift + residual term)."""
+    _need_gpu(m)
+    lib = _lib.load()
+    B, H, W = shape
+    T, Tp = wino4_tiles(B, H, W)
+    O = m.shape[-1]
+    if m.dtype != torch.float32 or m.shape != (36, Tp, O) or not m.is_contiguous():
+        raise ValueError(f"wino4_output needs a contiguous float32 [36, {Tp}, O] tensor, got {tuple(m.shape)}")
+    out = torch.empty(B, H, W, O, dtype=torch.float32, device=m.device)
+    r = rs = rb = None
+    if residual is not None:
+        r = residual if residual.is_contiguous() else residual.contiguous()
+        if r.shape != out.shape or r.dtype != torch.float32:
+            raise ValueError("residual shape / dtype mismatch")
+        if res_affine is not None:
+            rs, rb = res_affine
+    nbytes = 4 * (36 * T * O + out.numel() * (2 if r is not None else 1))
+    with torch.cuda.device(m.device), _lib.traced("wino4_output", nbytes, (O, T)):
+        rc = lib.ffb6d_wino4_output_f32(m.data_ptr(), scale.data_ptr(), shift.data_ptr(), r.data_ptr() if r is not None else None,
+                                        rs.data_ptr() if rs is not None else None, rb.data_ptr() if rb is not None else None,
+                                        out.data_ptr(), B, H, W, O, Tp, int(act), float(slope), _stream(m))
+    _lib.check(rc, "ffb6d_wino4_output_f32")
     return out
 
 

@@ -179,6 +179,16 @@ int ffb6d_wino_output_f32(const float* m, const float* scale, const float* shift
                           const float* rshift, float* out, int64_t B, int64_t H, int64_t W, int64_t O, int64_t Tp, int act, float slope,
                           ffb6d_stream_t stream);
 
+/* Winograd F(4x4,3x3) on the points 0, 1, -1, 2, -1/2 (csrc/winograd.h): the same pair for 6 x 6 windows at stride 4 and 4 x 4 output
+ * tiles.  T = B * ceil(H/4) * ceil(W/4) tiles numbered (b, ty, tx); Tp >= T, a multiple of 128; plane xi = 6u + v; 36 planes.
+ * input:  x [B,H,W,C] -> v [36][Tp][C] = B^T d B of the 6 x 6 window at (4ty - 1, 4tx - 1) with the integer B^T of csrc/winograd.h
+ *         (the inverse scale belongs in the filter transform), zeros outside the map; rows T..Tp-1 of a plane are left unwritten.
+ * output: m [36][Tp][O] -> out [B,H,W,O], the expression of ffb6d_wino_output_f32 on A^T m A; any H, W (stores masked per pixel). */
+int ffb6d_wino4_input_f32(const float* x, float* v, int64_t B, int64_t H, int64_t W, int64_t C, int64_t Tp, ffb6d_stream_t stream);
+int ffb6d_wino4_output_f32(const float* m, const float* scale, const float* shift, const float* res, const float* rscale,
+                           const float* rshift, float* out, int64_t B, int64_t H, int64_t W, int64_t O, int64_t Tp, int act, float slope,
+                           ffb6d_stream_t stream);
+
 /* Att_pooling.forward up to the pooled tensor (RandLANet.py:243-248) with the neighbour gather fused in:
  * S[(n,k),:] = [ f[nei[n,k],:] | g[(n,k),:] ], out[n,m] = sum_k S[(n,k),m] * softmax_k((S w_fc^T)[(n,k),m]).
  * f [B*N, ldf] point rows (c1 channels), nei [B,N,16] indices inside the frame, g [B*N*16, ldg] pair rows (c2 channels),

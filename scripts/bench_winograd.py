@@ -1,8 +1,8 @@
 #!/usr/bin/env python3
-"""One wide trunk convolution (3x3, stride 1, BatchNorm + residual + ReLU) alone on the chip, direct against Winograd F(2x2,3x3):
-MIOpen + affine_act_ against input transform -> batched GEMM -> output transform (forward_pm.conv_wino), each stage timed by itself
-with device events.  Prints one JSON line per width: microseconds per launch, the GEMM's TFLOP/s and its share of the fp32 MFMA peak,
-each transform's GB/s by algorithmic bytes.
+"""One wide trunk convolution (3x3, stride 1, BatchNorm + residual + ReLU) alone on the chip, direct against Winograd F(2x2,3x3) and
+F(4x4,3x3): MIOpen + affine_act_ against input transform -> batched GEMM -> output transform (forward_pm.conv_wino, m = 2 / 4), each
+stage timed by itself with device events.  Prints one JSON line per width: microseconds per launch, the GEMMs' TFLOP/s and their share
+of the fp32 MFMA peak (the F(4x4) GEMM also under every plan its tile_hint reaches), each transform's GB/s by algorithmic bytes.
 argv: [B H W] (default 8 60 80: the trunk map of the benchmark) [reps]"""
 import json
 import os
@@ -44,7 +44,7 @@ with torch.no_grad():
         rec = {"shape": [B, H, W, cin, cout], "tiles": T,
                "direct_conv_us": timed(lambda: forward_pm.conv(x, conv)),
                "direct_conv_affine_us": timed(lambda: ops_pm.affine_act_(forward_pm.conv(x, conv), scale, shift, act=ops.ACT_RELU, residual=res)),
-               "wino_total_us": timed(lambda: forward_pm.conv_wino(x, conv, scale, shift, residual=res)),
+               "wino_total_us": timed(lambda: forward_pm.conv_wino(x, conv, scale, shift, residual=res, m=2)),
                "wino_input_us": timed(lambda: ops_pm.wino_input(x, out=v)),
                "wino_gemm_us": timed(lambda: ops_pm.mlp_batched(v, u, out=m)),
                "wino_gemm_lds_form_us": timed(lambda: ops_pm.mlp_batched(v, u, out=m, tile_hint=7)),
@@ -54,5 +54,22 @@ with torch.no_grad():
         rec["wino_gemm_frac_of_fp32_mfma_peak"] = rec["wino_gemm_tflops"] / PEAK_TFLOPS
         rec["wino_input_GBps"] = 4.0 * (px * cin + 16 * T * cin) / rec["wino_input_us"] * 1e-3
         rec["wino_output_GBps"] = 4.0 * (16 * T * cout + 2 * px * cout) / rec["wino_output_us"] * 1e-3
+        T4, Tp4 = ops_pm.wino4_tiles(B, H, W)
+        u4 = forward_pm.wino4_weights(conv)
+        v4, m4 = ops_pm.wino4_input(x), torch.empty(36, Tp4, cout, device=dev)
+        ops_pm.mlp_batched(v4, u4, out=m4)
+        rec.update({"tiles4": T4, "variant": forward_pm.wino_variant(B, H, W),
+                    "wino4_total_us": timed(lambda: forward_pm.conv_wino(x, conv, scale, shift, residual=res, m=4)),
+                    "wino4_input_us": timed(lambda: ops_pm.wino4_input(x, out=v4)),
+                    "wino4_gemm_us": timed(lambda: ops_pm.mlp_batched(v4, u4, out=m4)),
+                    "wino4_gemm_lds_form_us": timed(lambda: ops_pm.mlp_batched(v4, u4, out=m4, tile_hint=7)),
+                    "wino4_output_us": timed(lambda: ops_pm.wino4_output(m4, (B, H, W), scale, shift, act=ops.ACT_RELU, residual=res))})
+        for plan in (1, 2, 4):                         # whole-point-tile plans: sequences of `plan` channel tiles (cout / 128 of them)
+            if plan * 128 <= cout:
+                rec["wino4_gemm_plan%d_us" % plan] = timed(lambda: ops_pm.mlp_batched(v4, u4, out=m4, tile_hint=8 + 256 * plan))
+        rec["wino4_gemm_tflops"] = 2.0 * 36 * T4 * cin * cout / rec["wino4_gemm_us"] * 1e-6
+        rec["wino4_gemm_frac_of_fp32_mfma_peak"] = rec["wino4_gemm_tflops"] / PEAK_TFLOPS
+        rec["wino4_input_GBps"] = 4.0 * (px * cin + 36 * T4 * cin) / rec["wino4_input_us"] * 1e-3
+        rec["wino4_output_GBps"] = 4.0 * (36 * T4 * cout + 2 * px * cout) / rec["wino4_output_us"] * 1e-3
         rec["direct_conv_tflops"] = 2.0 * 9 * px * cin * cout / rec["direct_conv_us"] * 1e-6
         print(json.dumps({k: (round(v, 3) if isinstance(v, float) else v) for k, v in rec.items()}), flush=True)
