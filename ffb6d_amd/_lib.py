@@ -127,6 +127,12 @@ SIGNATURES = {
     "ffb6d_render_set_form": (None, [_i32]),
     "ffb6d_render_f32": (_i32, [_vp, _vp, _vp, _vp, _vp, _i32, _i64, _i64, _i64, _i64, _vp, _vp, _vp, _i32, _vp, _i32, _i32, _i32,
                                 _c.c_float, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    # include/ffb6d_fps.h
+    "ffb6d_fps_resident_capacity": (_i32, []),
+    "ffb6d_fps_set_form": (None, [_i32]),
+    "ffb6d_fps_workspace_bytes": (_sz, [_i32, _i64, _i32]),
+    "ffb6d_fps_f32": (_i32, [_vp, _vp, _i32, _i64, _i64, _i32, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "ffb6d_box_info_f32": (_i32, [_vp, _vp, _i32, _i64, _vp, _vp, _vp, _vp]),
 }
 
 _LIB = None

@@ -149,7 +149,7 @@ def solve_poses(pcld, mask, ctr_of, kp_of, mesh_kps, mesh_ctr, r_lst=None, use_c
       pcld f32 [B,N,3]; mask int [B,N] predicted class per point (0 = background);
       ctr_of f32 [B,1,N,3], kp_of f32 [B,n_kps,N,3] (end_points['pred_ctr_ofs'/'pred_kp_ofs']);
       mesh_kps [n_cls,n_kps,3], mesh_ctr [n_cls,3] model-frame keypoints indexed by class id;
-      r_lst[cls_id-1] object radii (needed when refine_mask);
+      r_lst[cls_id-1] object radii (needed when refine_mask); all three host data or device tensors (objinfo.ObjectInfo);
       classes: None = every class present in a frame's mask (YCB flow, :82); or a list of class ids
                solved in every frame whether present or not (LineMOD flow: [1], :238-241);
       refine_mask: centre-clustering mask filter (:83-108); default = use_ctr_clus_flter and classes is None.
@@ -164,8 +164,10 @@ def solve_poses(pcld, mask, ctr_of, kp_of, mesh_kps, mesh_ctr, r_lst=None, use_c
     B, N, _ = pcld.shape
     n_kps = kp_of.shape[1]
     dev = pcld.device
-    mesh_kps = torch.as_tensor(np.asarray(mesh_kps, np.float32), device=dev)
-    mesh_ctr = torch.as_tensor(np.asarray(mesh_ctr, np.float32), device=dev)
+    # host data, or device tensors as objinfo.ObjectInfo holds them
+    on_device = lambda x: torch.is_tensor(x) and x.is_cuda                                                                  # noqa: E731
+    mesh_kps = mesh_kps.to(device=dev, dtype=torch.float32) if on_device(mesh_kps) else torch.as_tensor(np.asarray(mesh_kps, np.float32), device=dev)
+    mesh_ctr = mesh_ctr.to(device=dev, dtype=torch.float32) if on_device(mesh_ctr) else torch.as_tensor(np.asarray(mesh_ctr, np.float32), device=dev)
     n_cls = mesh_kps.shape[0]
     if refine_mask is None:
         refine_mask = use_ctr_clus_flter and classes is None
@@ -200,7 +202,10 @@ def solve_poses(pcld, mask, ctr_of, kp_of, mesh_kps, mesh_ctr, r_lst=None, use_c
         begin = np.zeros(B + 1, np.int32)
         np.add.at(begin, frame_np + 1, 1)
         pair_begin = _i32(np.cumsum(begin), dev)
-        max_dist = torch.tensor([np.float32(float(r_lst[c - 1]) * 0.8) for c in class_np], dtype=torch.float32, device=dev)
+        if on_device(r_lst):                                    # the same product, in double, without reading the radii back
+            max_dist = (r_lst.to(device=dev, dtype=torch.float64)[class_of.long() - 1] * 0.8).float()
+        else:
+            max_dist = torch.tensor([np.float32(float(r_lst[c - 1]) * 0.8) for c in class_np], dtype=torch.float32, device=dev)
         new_mask = torch.empty_like(mask)
         with torch.cuda.device(dev):
             rc = lib.ffb6d_refine_mask_by_center(pcld.data_ptr(), ctr_of.data_ptr(), mask.data_ptr(), _mask_bits(mask),
