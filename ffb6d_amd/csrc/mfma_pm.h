@@ -72,6 +72,24 @@ __device__ __forceinline__ void mfma_step(f32x16 (&acc)[TM][TN], const u32x4 (&a
     }
 }
 
+// v_mfma_f32_16x16x4_f32 (csrc/winograd_fused.h): lane l supplies A[i = l&15][k = l>>4] and B[k = l>>4][j = l&15]; accumulator register r
+// of lane l is D[i = 4*(l>>4) + r][j = l&15].  Where the compiler has no such instruction (a host build of the kernel sources), the same
+// layouts restated with wave shuffles; `threadIdx.x & 63` is the lane (one-dimensional workgroups of whole waves).
+typedef float f32x4 __attribute__((ext_vector_type(4)));
+__device__ __forceinline__ f32x4 mfma_16x16x4(float a, float b, f32x4 c)
+{
+#if __has_builtin(__builtin_amdgcn_mfma_f32_16x16x4f32)
+    return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0);
+#else
+    const int l = (int)(threadIdx.x & 63u);
+    for (int k = 0; k < 4; ++k) {
+        const float bk = __shfl(b, 16 * k + (l & 15), 64);
+        for (int r = 0; r < 4; ++r) c[r] = fmaf(__shfl(a, 16 * k + 4 * (l >> 4) + r, 64), bk, c[r]);
+    }
+    return c;
+#endif
+}
+
 // act(v) = max(v, slope * v): slope 1 = identity, 0 = ReLU, 0.2 = LeakyReLU(0.2) -- no branch on the activation code
 __device__ __forceinline__ float activate(float v, float slope) { return fmaxf(v, slope * v); }
 

@@ -22,6 +22,7 @@
 #include "ffb6d_ops.h"
 #include "row_unit.h"
 #include "winograd.h"
+#include "winograd_fused.h"
 
 namespace ffb6d {
 namespace {
@@ -624,6 +625,13 @@ int ffb6d_wino4_output_f32(const float* m, const float* scale, const float* shif
                            ffb6d_stream_t stream)
 {
     return wino::output4_f32(m, scale, shift, res, rscale, rshift, out, B, H, W, O, Tp, act, slope, stream);
+}
+
+int ffb6d_wino4_conv_f32(const float* x, const float* u, const float* scale, const float* shift, const float* res, const float* rscale,
+                         const float* rshift, float* out, int64_t B, int64_t H, int64_t W, int64_t C, int64_t O, int act, float slope,
+                         int form, ffb6d_stream_t stream)
+{
+    return wino::conv4_f32(x, u, scale, shift, res, rscale, rshift, out, B, H, W, C, O, act, slope, form, stream);
 }
 
 int ffb6d_affine_relu_maxpool_pm(int dtype, const void* x, const float* scale, const float* shift, void* out, int64_t B, int64_t IH,

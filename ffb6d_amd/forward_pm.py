@@ -265,7 +265,8 @@ def conv(x, c):
 # BatchNorm / residual / ReLU pass of the block fused in (csrc/winograd.h).  False: MIOpen + affine_act_ for
 # those layers too.  Within HOT_TOL of the direct form (measured <= 1.8e-6 of range on outputs and stage taps), not equal bits; the
 # converted layers repeat their bits from run to run.  Measured (profiles/winograd_trunk_ab.json): step 20.05 -> 15.66 ms; with the
-# threshold at 512 17.2 ms -- the eleven 256-wide layers are worth 1.5 ms, so the threshold is 256 (the 64- and 128-wide layers: not built).
+# threshold at 512 17.2 ms -- the eleven 256-wide layers are worth 1.5 ms, so the threshold is 256 (the 64- and 128-wide layers
+# take the fused kernel below: TRUNK_WINOGRAD_FUSED).
 TRUNK_WINOGRAD = True
 TRUNK_WINOGRAD_MIN_CIN = 256
 
@@ -350,19 +351,66 @@ def conv_wino(x, c, scale, shift, residual=None, res_affine=None, m=None):
     return ops_pm.wino_output(mm, x.shape[:3], scale, shift, act=ops.ACT_RELU, residual=residual, res_affine=res_affine)
 
 
+# The narrow stride-1 3x3 convolutions of the trunk (fp32; 64 -> 64 on the quarter-resolution map, 128 -> 128 and 128 -> 256 on the eighth-
+# resolution one) as Winograd F(4x4,3x3) in ONE launch (csrc/winograd_fused.h): V stays in LDS, M in registers, the
+# BatchNorm / residual / ReLU pass is the kernel's epilogue, so MIOpen's convolution, its zero-fill and affine_act_ all go.  The unfused
+# three-kernel path is no candidate at these widths: V and M are 2.25 maps each way and the batched GEMM needs K >= 128.  F(4x4) on every
+# map (tile padding costs the fused kernel no GEMM rows).  TRUNK_WINOGRAD_FUSED_WIDTHS is the per-width rule: the (Cin, Cout) pairs where
+# the kernel beat MIOpen + its passes alone on the chip (profiles/winograd_narrow_layers.jsonl: 86 against 142 us at 64 -> 64, 98 against 128
+# at 128 -> 128, 149 against 237 at 128 -> 256).  False: MIOpen + affine_act_ for these layers, bit for bit what ran before the kernel existed.
+# Within HOT_TOL of the direct form (measured <= 1.9e-6 of range on outputs and stage taps).  Measured (profiles/winograd_narrow_ab.json):
+# step 13.01 - 13.06 -> 12.60 - 12.64 ms.
+TRUNK_WINOGRAD_FUSED = True
+TRUNK_WINOGRAD_FUSED_WIDTHS = frozenset({(64, 64), (128, 128), (128, 256)})
+
+
+def wino_fused_ok(c, x):
+    """Does convolution `c` on the [B,H,W,C] map x take the fused F(4x4) kernel?  fp32 inference, 3x3 / stride 1 / padding 1 / dilation 1 /
+    one group / no bias, a (Cin, Cout) of TRUNK_WINOGRAD_FUSED_WIDTHS, map and output < 2 GiB."""
+    if not (TRUNK_WINOGRAD and TRUNK_WINOGRAD_FUSED) or x.dtype != torch.float32 or c.weight.dtype != torch.float32:
+        return False
+    if (c.kernel_size, c.stride, c.padding, c.dilation, c.groups) != ((3, 3), (1, 1), (1, 1), (1, 1), 1) or c.bias is not None \
+            or c.padding_mode != "zeros":
+        return False
+    cout, cin = c.weight.shape[:2]
+    if (cin, cout) not in TRUNK_WINOGRAD_FUSED_WIDTHS or cin not in ops_pm.WINO4_CONV_CIN or cout not in ops_pm.WINO4_CONV_COUT:
+        return False
+    B, H, W, _ = x.shape
+    return B * H * W * max(cin, cout) * 4 < (1 << 31) - (1 << 20)
+
+
+def conv_wino_fused(x, c, scale, shift, residual=None, res_affine=None):
+    """relu(scale * conv3x3(x) + shift + residual term) of a [B,H,W,C] map by the fused F(4x4) kernel"""
+    x = x if x.is_contiguous() else x.contiguous()
+    return ops_pm.wino4_conv(x, wino4_weights(c), scale, shift, act=ops.ACT_RELU, residual=residual, res_affine=res_affine)
+
+
+def trunk_conv_form(c, x):
+    """Which of the three forms convolution `c` of a residual block takes on the map x: "fused" (one launch), "wino" (input transform ->
+    batched GEMM -> output transform) or "miopen" (+ affine_act_)"""
+    if wino_fused_ok(c, x):
+        return "fused"
+    return "wino" if wino_ok(c, x) else "miopen"
+
+
 def res_block(rb, x):
     """extractors.py:49-63 (BasicBlock): BN+ReLU and BN+residual(+BN of the projection)+ReLU as one pass each."""
-    if wino_ok(rb.conv1, x):
+    form1 = trunk_conv_form(rb.conv1, x)
+    if form1 == "fused":
+        y = conv_wino_fused(x, rb.conv1, *ops.bn_fold(rb.bn1))
+    elif form1 == "wino":
         y = conv_wino(x, rb.conv1, *ops.bn_fold(rb.bn1))
     else:
         y = ops_pm.affine_act_(conv(x, rb.conv1), *ops.bn_fold(rb.bn1), act=ops.ACT_RELU)
-    wino2 = wino_ok(rb.conv2, y)
-    if not wino2:
+    form2 = trunk_conv_form(rb.conv2, y)
+    if form2 == "miopen":
         y = conv(y, rb.conv2)
     res, res_affine = x, None
     if rb.downsample is not None:
         res, res_affine = conv(x, rb.downsample[0]), ops.bn_fold(rb.downsample[1])
-    if wino2:
+    if form2 == "fused":
+        return conv_wino_fused(y, rb.conv2, *ops.bn_fold(rb.bn2), residual=res, res_affine=res_affine)
+    if form2 == "wino":
         return conv_wino(y, rb.conv2, *ops.bn_fold(rb.bn2), residual=res, res_affine=res_affine)
     return ops_pm.affine_act_(y, *ops.bn_fold(rb.bn2), act=ops.ACT_RELU, residual=res, res_affine=res_affine)
 

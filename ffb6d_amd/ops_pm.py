@@ -267,6 +267,44 @@ def wino4_output(m, shape, scale, shift, act=ACT_NONE, slope=0.0, residual=None,
     return out
 
 
+WINO4_CONV_CIN = (64, 128)
+WINO4_CONV_COUT = (64, 128, 256)
+
+
+def wino4_conv(x, u, scale, shift, act=ACT_NONE, slope=0.0, residual=None, res_affine=None, out=None, form=0):
+    """3x3 / stride 1 / padding 1 convolution by Winograd F(4x4,3x3) in one launch, with the glue of affine_act_ on the way out
+    (csrc/winograd_fused.h): x [B,H,W,C] fp32, u [36,O,C] = forward_pm.wino4_filter(weight) -> [B,H,W,O] = act(scale * conv(x) + shift +
+    residual term).  C in WINO4_CONV_CIN, O in WINO4_CONV_COUT.  `out` (contiguous [B,H,W,O]) may alias neither x nor the residual.
+    form: 0 = automatic, 1 / 2 = the kernel's two workgroup shapes (tests, measurements)."""
+    _need_gpu(x, u)
+    lib = _lib.load()
+    if x.dtype != torch.float32 or x.dim() != 4 or not x.is_contiguous():
+        raise ValueError("wino4_conv needs a contiguous float32 [B,H,W,C] map")
+    B, H, W, C = x.shape
+    if u.dtype != torch.float32 or u.dim() != 3 or u.shape[0] != 36 or u.shape[2] != C or not u.is_contiguous():
+        raise ValueError(f"wino4_conv needs a contiguous float32 filter [36, O, {C}], got {tuple(u.shape)}")
+    O = u.shape[1]
+    if out is None:
+        out = torch.empty(B, H, W, O, dtype=torch.float32, device=x.device)
+    if out.shape != (B, H, W, O) or not out.is_contiguous() or out.dtype != torch.float32:
+        raise ValueError(f"out must be contiguous float32 [{B}, {H}, {W}, {O}]")
+    r = rs = rb = None
+    if residual is not None:
+        r = residual if residual.is_contiguous() else residual.contiguous()
+        if r.shape != out.shape or r.dtype != torch.float32:
+            raise ValueError("residual shape / dtype mismatch")
+        if res_affine is not None:
+            rs, rb = res_affine
+    nbytes = 4 * (x.numel() + u.numel() + out.numel() * (2 if r is not None else 1))
+    with torch.cuda.device(x.device), _lib.traced("wino4_conv", nbytes, (C, O, B * H * W)):
+        rc = lib.ffb6d_wino4_conv_f32(x.data_ptr(), u.data_ptr(), scale.data_ptr(), shift.data_ptr(),
+                                      r.data_ptr() if r is not None else None, rs.data_ptr() if rs is not None else None,
+                                      rb.data_ptr() if rb is not None else None, out.data_ptr(), B, H, W, C, O, int(act), float(slope),
+                                      int(form), _stream(x))
+    _lib.check(rc, "ffb6d_wino4_conv_f32")
+    return out
+
+
 def att_pool(f, nei_idx, g, w_fc, out=None):
     """Att_pooling.forward up to the pooled tensor (RandLANet.py:243-248) with the neighbour gather fused in.
     f [B,N,C1] point features, nei_idx [B,N,16], g [B,N,16,C2] per-pair features, w_fc [C1+C2, C1+C2] (fc conv weight)

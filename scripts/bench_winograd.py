@@ -3,7 +3,12 @@
 F(4x4,3x3): MIOpen + affine_act_ against input transform -> batched GEMM -> output transform (forward_pm.conv_wino, m = 2 / 4), each
 stage timed by itself with device events.  Prints one JSON line per width: microseconds per launch, the GEMMs' TFLOP/s and their share
 of the fp32 MFMA peak (the F(4x4) GEMM also under every plan its tile_hint reaches), each transform's GB/s by algorithmic bytes.
-argv: [B H W] (default 8 60 80: the trunk map of the benchmark) [reps]"""
+argv: [B H W] (default 8 60 80: the trunk map of the benchmark) [reps]
+
+argv: narrow [reps] -- the narrow trunk layers instead, (8,120,160,64->64), (8,60,80,128->128) and (8,60,80,128->256): MIOpen's convolution +
+affine_act_ with the pinned find-db as bench.py uses it (device events around the pair, so MIOpen's zero-fill is inside), the unfused F(4x4)
+path where the batched GEMM accepts the shape, and the fused kernel (csrc/winograd_fused.h) in both workgroup shapes; TFLOP/s of the fused
+kernel by the Winograd multiplies, GB/s by x + residual + out.  One JSON line per shape (profiles/winograd_narrow_layers.jsonl)."""
 import json
 import os
 import sys
@@ -15,8 +20,14 @@ from ffb6d_amd import forward_pm, ops, ops_pm
 
 PEAK_TFLOPS = 157.3        # fp32 MFMA, MI355X
 dev = torch.device("cuda:0")
-B, H, W = (int(v) for v in sys.argv[1:4]) if len(sys.argv) > 3 else (8, 60, 80)
-reps = int(sys.argv[4]) if len(sys.argv) > 4 else 20
+NARROW = len(sys.argv) > 1 and sys.argv[1] == "narrow"
+if NARROW:
+    from ffb6d_amd import miopen_pin
+    MIOPEN_DB = miopen_pin.use(only_solver=miopen_pin.FWD_SOLVER)
+    reps = int(sys.argv[2]) if len(sys.argv) > 2 else 50
+else:
+    B, H, W = (int(v) for v in sys.argv[1:4]) if len(sys.argv) > 3 else (8, 60, 80)
+    reps = int(sys.argv[4]) if len(sys.argv) > 4 else 20
 torch.manual_seed(0)
 
 
@@ -32,8 +43,34 @@ def timed(fn):
     return 1e3 * a.elapsed_time(b) / reps
 
 
+def narrow():
+    for B, H, W, cin, cout in ((8, 120, 160, 64, 64), (8, 60, 80, 128, 128), (8, 60, 80, 128, 256)):
+        conv = torch.nn.Conv2d(cin, cout, 3, 1, 1, bias=False).to(dev)
+        x, res = torch.randn(B, H, W, cin, device=dev), torch.randn(B, H, W, cout, device=dev)
+        scale, shift = torch.rand(cout, device=dev) + .5, torch.randn(cout, device=dev)
+        u4 = forward_pm.wino4_weights(conv)
+        out = torch.empty(B, H, W, cout, device=dev)
+        px, T4 = B * H * W, ops_pm.wino4_tiles(B, H, W)[0]
+        rec = {"shape": [B, H, W, cin, cout], "tiles4": T4, "miopen": MIOPEN_DB,
+               "direct_conv_us": timed(lambda: forward_pm.conv(x, conv)),
+               "direct_conv_affine_us": timed(lambda: ops_pm.affine_act_(forward_pm.conv(x, conv), scale, shift, act=ops.ACT_RELU, residual=res))}
+        if forward_pm.wino_ok(conv, x, m=4) or (cin >= 128 and cin % 32 == 0):
+            rec["wino4_unfused_total_us"] = timed(lambda: forward_pm.conv_wino(x, conv, scale, shift, residual=res, m=4))
+        for form in (1, 2):
+            rec["fused_form%d_us" % form] = timed(lambda: ops_pm.wino4_conv(x, u4, scale, shift, act=ops.ACT_RELU, residual=res, out=out,
+                                                                             form=form))
+        rec["fused_us"] = timed(lambda: ops_pm.wino4_conv(x, u4, scale, shift, act=ops.ACT_RELU, residual=res, out=out))
+        rec["fused_tflops"] = 2.0 * 36 * T4 * cin * cout / rec["fused_us"] * 1e-6
+        rec["fused_frac_of_fp32_mfma_peak"] = rec["fused_tflops"] / PEAK_TFLOPS
+        rec["fused_GBps"] = 4.0 * px * (cin + 2 * cout) / rec["fused_us"] * 1e-3
+        rec["direct_conv_tflops"] = 2.0 * 9 * px * cin * cout / rec["direct_conv_us"] * 1e-6
+        print(json.dumps({k: (round(v, 3) if isinstance(v, float) else v) for k, v in rec.items()}), flush=True)
+
+
 with torch.no_grad():
-    for cin, cout in ((256, 256), (256, 512), (512, 512)):
+    if NARROW:
+        narrow()
+    for cin, cout in () if NARROW else ((256, 256), (256, 512), (512, 512)):
         conv = torch.nn.Conv2d(cin, cout, 3, 1, 1, bias=False).to(dev)
         x, res = torch.randn(B, H, W, cin, device=dev), torch.randn(B, H, W, cout, device=dev)
         scale, shift = torch.rand(cout, device=dev) + .5, torch.randn(cout, device=dev)
