@@ -123,6 +123,9 @@ SIGNATURES = {
     "ffb6d_rgb_hsv_jitter": (_i32, [_vp, _vp, _vp, _i32, _i64, _i64, _vp]),
     "ffb6d_rgb_stencil": (_i32, [_vp, _vp, _c.c_uint64, _vp, _i32, _i64, _i64, _vp]),
     "ffb6d_add_real_back": (_i32, [_vp, _vp, _i32, _vp, _vp, _vp, _vp, _i32, _i32, _vp, _vp, _vp, _i32, _i64, _vp]),
+    "ffb6d_jitter_frames_check": (_i32, [_vp, _i32]),
+    "ffb6d_color_jitter_workspace_bytes": (_sz, [_i32, _i64, _i64]),
+    "ffb6d_color_jitter_u8": (_i32, [_vp, _vp, _vp, _i32, _i64, _i64, _vp, _sz, _vp]),
     # include/ffb6d_render.h
     "ffb6d_render_workspace_bytes": (_sz, [_i32, _i64, _i32, _i32, _i32]),
     "ffb6d_render_set_form": (None, [_i32]),

@@ -6,8 +6,10 @@ the C ABI of include/ffb6d_train.h.
     motion_blur_taps        linear_motion_blur's kernel    ycb_dataset.py:88-105 (cv2.line restated)
     rgb_add_noise           rgb_add_noise on the device    HSV, sharpen, motion blur, Gaussian blur, Gaussian noise
     add_real_back           add_real_back                  ycb_dataset.py:145-163, linemod_dataset.py:166-186
-    assemble_training_batch the order of ycb_dataset.py:198-204 / linemod_dataset.py:241-249, then inputs.assemble_inputs
-                            and pose_targets
+    draw_jitter_params      ColorJitter's host draws       transforms.ColorJitter(0.2, 0.2, 0.2, 0.05), ycb_dataset.py:34
+    color_jitter            self.trancolor on the device   ycb_dataset.py:190-193, linemod_dataset.py:221-223
+    assemble_training_batch color_jitter at decode time, the order of ycb_dataset.py:198-204 / linemod_dataset.py:241-249, then
+                            inputs.assemble_inputs and pose_targets
 
 Randomness.  Stage decisions and scalar parameters are drawn on the host from a numpy RandomState in the reference's exact
 order, so a frame gets the reference's decisions and parameters up to and including the noise sigma.  The per-pixel normals
@@ -17,6 +19,9 @@ RandomState and is therefore distribution-equivalent, not draw-identical.
 
 OpenCV is not available where this package is built: the HSV round trip, filter2D / GaussianBlur and cv2.line are restated
 from OpenCV's published algorithms and pinned against those restatements (tests/train_data_ref.py), not against cv2.
+Pillow is available there, and torchvision's PIL ColorJitter is a thin layer over it: color_jitter is pinned to Pillow's own
+bytes (tests/golden/color_jitter.npz, tests/color_jitter_ref.py).  Its planes are R, G, B in that order, whereas plane 0 plays
+OpenCV's "B" in rgb_add_noise; both are the same array, as in the reference.
 There is no CPU fallback: CPU tensors raise FFB6DNativeError.
 """
 
@@ -30,6 +35,9 @@ MAX_TAPS, MAX_HALO = 32, 15
 # ffb6d_stencil_frame_t of include/ffb6d_train.h (all fields 4 bytes wide: no padding)
 STENCIL_FRAME = np.dtype([("n_taps", "<i4"), ("halo", "<i4"), ("sigma", "<f4"), ("extra_sigma", "<f4"),
                           ("dy", "<i4", MAX_TAPS), ("dx", "<i4", MAX_TAPS), ("w", "<f4", MAX_TAPS)])
+# ffb6d_jitter_frame_t of include/ffb6d_train.h
+JITTER_FRAME = np.dtype([("n_ops", "<i4"), ("op", "<i4", 4), ("alpha", "<f4", 4), ("hue_shift", "<i4")])
+JITTER_OPS = ("brightness", "contrast", "saturation", "hue")       # FFB6D_JITTER_*; torchvision's fn_idx
 FLAVOURS = ("ycb", "linemod")
 EXTRA_NOISE_SIGMA = 7.0                     # ycb_dataset.py:141
 
@@ -360,6 +368,86 @@ def rgb_add_noise(rgb, params, seed):
 
 
 # ---------------------------------------------------------------------------------------------------------------------
+# ColorJitter
+# ---------------------------------------------------------------------------------------------------------------------
+def draw_jitter_params(generator, brightness=0.2, contrast=0.2, saturation=0.2, hue=0.05):
+    """The host draws of one frame's ColorJitter from a torch.Generator (CPU): randperm(4) gives the order, then one uniform
+    draw each from [1 - b, 1 + b] (floored at 0), [1 - c, 1 + c], [1 - s, 1 + s] and [-h, h]; the defaults are the reference's
+    transforms.ColorJitter(0.2, 0.2, 0.2, 0.05).  An amplitude of None or 0 leaves the operation out.  torchvision is not
+    available where this package is built, so this is distribution-equivalent to ColorJitter.get_params, not draw-identical to
+    any torchvision release; color_jitter takes explicit orders and factors, so a caller with torchvision can pass its own.
+    Returns dict(order=(...), brightness=, contrast=, saturation=, hue=) with the keys of the operations that are on."""
+    p = dict(order=tuple(int(i) for i in torch.randperm(4, generator=generator)))
+    for key, amp in zip(JITTER_OPS, (brightness, contrast, saturation, hue)):
+        if not amp:
+            continue
+        if amp < 0 or (key == "hue" and amp > 0.5):
+            raise ValueError(f"{key} amplitude {amp} outside its range")
+        lo, hi = (-amp, amp) if key == "hue" else (max(0.0, 1.0 - amp), 1.0 + amp)
+        p[key] = lo + (hi - lo) * float(torch.rand(1, generator=generator, dtype=torch.float64))
+    return p
+
+
+def jitter_records(params):
+    """One ffb6d_jitter_frame_t per frame from the per-frame dicts of color_jitter (host side, numpy)."""
+    rec = np.zeros(len(params), JITTER_FRAME)
+    for b, p in enumerate(params):
+        if p is None:
+            continue
+        order = p.get("order", (0, 1, 2, 3))
+        if len(order) > 4:
+            raise ValueError(f"frame {b}: order {tuple(order)} holds more than four operations")
+        n = 0
+        for o in order:
+            op = int(o)
+            if not 0 <= op < 4:
+                raise ValueError(f"frame {b}: unknown operation {o!r} in order")
+            val = p.get(JITTER_OPS[op])
+            if val is None:
+                continue
+            if op == 3:
+                if not -0.5 <= float(val) <= 0.5:
+                    raise ValueError(f"frame {b}: hue {val} outside [-0.5, 0.5]")
+                rec[b]["hue_shift"] = int(float(val) * 255.0) % 256     # truncated toward zero, then np.uint8's wrap-around
+            else:
+                rec[b]["alpha"][n] = np.float32(val)
+            rec[b]["op"][n] = op
+            n += 1
+        rec[b]["n_ops"] = n
+    return rec
+
+
+def color_jitter(rgb, params):
+    """torchvision's PIL ColorJitter of B frames on the device, byte for byte (include/ffb6d_train.h states the rule).
+    rgb uint8 [B,3,H,W], planes R, G, B; params: one entry per frame, dict(order=(...), brightness=, contrast=, saturation=,
+    hue=): `order` lists the operations (0 brightness, 1 contrast, 2 saturation, 3 hue: torchvision's ids) as they are applied, an
+    operation whose key is missing or None is skipped, and an entry of None passes the frame unchanged (draw_jitter_params
+    makes such dicts).  A repeated operation, a negative or non-finite factor or a hue outside [-0.5, 0.5] raises before
+    anything is launched.  One upload carries the records; two launches do the batch.  Returns a new uint8 tensor."""
+    x = _u8_images(rgb)
+    B, _, H, W = x.shape
+    if len(params) != B:
+        raise ValueError(f"{len(params)} parameter sets for {B} frames")
+    rec = jitter_records(params)
+    lib = _lib.load()
+    _lib.check(lib.ffb6d_jitter_frames_check(rec.ctypes.data, B), "ffb6d_jitter_frames_check")
+    out = torch.empty_like(x)
+    if x.numel() == 0:
+        return out
+    dev = x.device
+    contrast = int(sum(1 in r["op"][:r["n_ops"]] for r in rec))
+    need = int(lib.ffb6d_color_jitter_workspace_bytes(B, H, W))
+    # records and workspace in one buffer: the records behind the workspace, which is a multiple of 256 bytes
+    buf = torch.empty(need + rec.nbytes, dtype=torch.uint8, device=dev)
+    buf[need:].copy_(torch.from_numpy(rec.view(np.uint8).reshape(-1)), non_blocking=False)
+    with torch.cuda.device(dev), _lib.traced("color_jitter", 3 * H * W * (2 * B + contrast), (B, H, W)):
+        rc = lib.ffb6d_color_jitter_u8(x.data_ptr(), buf.data_ptr() + need, out.data_ptr(), B, H, W, buf.data_ptr(), need,
+                                       _stream(x))
+    _lib.check(rc, "ffb6d_color_jitter_u8")
+    return out
+
+
+# ---------------------------------------------------------------------------------------------------------------------
 # background compositing
 # ---------------------------------------------------------------------------------------------------------------------
 def _mask_u8_or_i32(t, name, B, H, W):
@@ -416,10 +504,12 @@ def _sub(t, idx):
 def assemble_training_batch(rgb, depth, label_img, K, n_points, cls_ids, RTs, mesh_kps, mesh_ctr, cam_scale=1.0,
                             normals=None, synthetic=None, noise_params=None, back=None, second_noise_params=None,
                             flavour="ycb", composite_rgb=None, fill_missing=False, depth_to_mm=1.0, seed=None,
-                            aug_seed=None, generator=None, index_dtype=torch.int64):
+                            aug_seed=None, generator=None, index_dtype=torch.int64, jitter_params=None):
     """Decoded training frames -> the network's inputs plus the loss's targets, all on the device.
       rgb uint8 [B,3,H,W], depth float32 [B,H,W] (raw units, metres = depth / cam_scale), label_img [B,H,W] uint8 / int32,
       K intrinsics, n_points; cls_ids / RTs / mesh_kps / mesh_ctr as in pose_targets.
+      jitter_params: None, or one color_jitter entry per frame (None = that frame unchanged), applied first, to real and
+        synthetic frames alike: the reference jitters at decode time (ycb_dataset.py:190-193, linemod_dataset.py:221-223).
       synthetic: per-frame flags (host); for those frames, in the reference's order (ycb_dataset.py:198-204,
         linemod_dataset.py:243-249): rgb_add_noise with noise_params[b], add_real_back with back = dict(rgb=, depth=, label=)
         (the real frames, one per synthetic frame, in order) and composite_rgb, then rgb_add_noise again with
@@ -432,6 +522,8 @@ def assemble_training_batch(rgb, depth, label_img, K, n_points, cls_ids, RTs, me
     _gpu(rgb, depth, label_img)
     B = int(rgb.shape[0])
     dev = rgb.device
+    if jitter_params is not None:
+        rgb = color_jitter(rgb, jitter_params)
     syn = [] if synthetic is None else [b for b in range(B) if bool(synthetic[b])]
     if syn:
         if aug_seed is None:

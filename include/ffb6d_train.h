@@ -6,9 +6,10 @@
  *   ffb6d_rgb_stencil         rgb_add_noise, filter2D / GaussianBlur stages and the Gaussian noise
  *                                                             ycb_dataset.py:82-143, linemod_dataset.py:117-164
  *   ffb6d_add_real_back       add_real_back                  ycb_dataset.py:145-163, linemod_dataset.py:166-186
+ *   ffb6d_color_jitter_u8     self.trancolor (ColorJitter)   ycb_dataset.py:34,190-193, linemod_dataset.py:35,221-223
  *
  * All pointers are DEVICE pointers.  Return value: 0 or an FFB6D_ERR_* code (text through ffb6d_last_error()); on an
- * error nothing is written.  No call reads anything back or waits: each enqueues one kernel on `stream`.
+ * error nothing is written.  No call reads anything back or waits: each enqueues one kernel on `stream` (ffb6d_color_jitter_u8: two).
  * OpenCV is not available where this library is built: the HSV and filter arithmetic below restates OpenCV's published
  * 8-bit algorithms (color_hsv.simd.hpp, filter.simd.hpp, drawing.cpp) and is pinned against those restatements only.
  */
@@ -111,6 +112,70 @@ int ffb6d_add_real_back(const uint8_t* rgb, const void* label, int label_u8, con
                         const float* back_depth, const void* back_mask, int back_mask_u8, int flavour,
                         const uint8_t* composite_rgb, uint8_t* rgb_out, float* depth_out, int B, int64_t HW,
                         ffb6d_stream_t stream);
+
+/* ColorJitter of B uint8 images [B,3,H,W]: torchvision's transforms.ColorJitter on its PIL backend, which the reference applies to
+ * every decoded frame when add_noise is on (self.trancolor, linemod_dataset.py:35,221-223, ycb_dataset.py:34,190-193).  That
+ * backend is a thin layer over Pillow (ImageEnhance.Brightness / Contrast / Color, an HSV round trip with a uint8 hue shift), and
+ * Pillow is installed where this library is built: the rule below is held to Pillow's own bytes (tests/golden/color_jitter.npz,
+ * tests/test_color_jitter_cpu.py), not to a restatement alone.
+ * Layout: plane 0 = R, plane 1 = G, plane 2 = B.  NOT the convention of the OpenCV stages above, where plane 0 plays "B": the
+ * reference jitters the PIL image (RGB) before it becomes the array that rgb_add_noise hands to OpenCV.
+ * A frame carries a chain of at most four operations, applied in the frame's own order, each to the uint8 result of the one before.
+ *   L(r,g,b) = (r 19595 + g 38470 + b 7471 + 0x8000) >> 16                                        (Pillow's RGB -> L)
+ *   blend(d, x, alpha): t = (float)d + alpha * ((float)x - (float)d)    float32, product and sum rounded separately (no FMA)
+ *                       out = t <= 0 ? 0 : t >= 255 ? 255 : (uint8)t    (truncation)
+ *   FFB6D_JITTER_BRIGHTNESS  blend(0, x, alpha)
+ *   FFB6D_JITTER_CONTRAST    blend(m, x, alpha) on every channel, m = (int)((double)sum L / (double)(H W) + 0.5); the sum runs over
+ *                            the whole frame AS IT STANDS when the contrast is reached, i.e. after the operations before it
+ *   FFB6D_JITTER_SATURATION  blend(L(pixel), x, alpha)
+ *   FFB6D_JITTER_HUE         RGB -> HSV, h' = (h + hue_shift) & 255, HSV -> RGB; alpha is not used.  hue_shift = (int)(hue * 255.0)
+ *                            truncated toward zero, modulo 256 (hue = -0.05 gives 244: np.uint8 wrap-around in torchvision)
+ *   RGB -> HSV: V = max; max == min: H = S = 0; otherwise
+ *     cr = (float)(max - min), s = cr / (float)max, rc, gc, bc = (float)(max - c) / cr                       (float32 quotients)
+ *     h = r == max ? bc - gc : g == max ? 2.0 + rc - bc : 4.0 + gc - rc         in double from the float32 quotients, then (float)
+ *     h = fmod(h / 6.0 + 1.0, 1.0)                                              in double, then (float)
+ *     H = clip((int)(h * 255.0), 0, 255), S = clip((int)(s * 255.0), 0, 255)    products in double
+ *   HSV -> RGB: S == 0: R = G = B = V; otherwise, all float32:
+ *     hh = (float)H * 6 / 255, i = floor(hh), f = hh - i, fs = (float)S / 255
+ *     p = round(V (1 - fs)), q = round(V (1 - fs f)), t = round(V (1 - fs (1 - f)))      C round, clipped to 0..255
+ *     (R,G,B) = [(V,t,p), (q,V,p), (p,V,t), (p,q,V), (t,p,V), (V,p,q)][i mod 6] */
+#define FFB6D_JITTER_BRIGHTNESS 0
+#define FFB6D_JITTER_CONTRAST 1
+#define FFB6D_JITTER_SATURATION 2
+#define FFB6D_JITTER_HUE 3
+#define FFB6D_JITTER_MAX_OPS 4
+
+/* One frame's chain (host-built, uploaded as an array of B; every field 4 bytes wide: no padding). */
+typedef struct {
+    int32_t n_ops;                        /* 0: the frame is copied; at most FFB6D_JITTER_MAX_OPS */
+    int32_t op[FFB6D_JITTER_MAX_OPS];     /* FFB6D_JITTER_* in the order of application, no operation twice */
+    float alpha[FFB6D_JITTER_MAX_OPS];    /* factor of op[i], finite and >= 0 (not used for the hue) */
+    int32_t hue_shift;                    /* 0..255 */
+} ffb6d_jitter_frame_t;
+
+/* Checks B records in HOST memory: FFB6D_ERR_ARG for n_ops outside [0, 4], an unknown or a repeated operation, a negative or
+ * non-finite factor, a hue_shift outside [0, 255].  ffb6d_color_jitter_u8 takes its records in device memory and reads nothing
+ * back, so it cannot refuse a bad record itself: callers check them here before the upload (ffb6d_amd.train_data does), and the
+ * kernels, for which the same predicate holds, copy a frame whose record fails it. */
+int ffb6d_jitter_frames_check(const ffb6d_jitter_frame_t* host_frames, int B);
+
+/* Bytes of device workspace for ffb6d_color_jitter_u8 (per-workgroup luminance sums; 0 for an empty batch). */
+size_t ffb6d_color_jitter_workspace_bytes(int B, int64_t H, int64_t W);
+
+/* The whole batch in two launches, whatever the per-frame orders; no read-back, no host wait.
+ *   sum pass    frames whose chain holds a contrast: every lane applies the operations BEFORE the contrast to its pixels in
+ *               registers and adds their L; each workgroup writes one 64-bit integer partial sum into the workspace (integer sums
+ *               are exact in any order; partial sums rather than an atomic into a slot, so that no third launch has to zero the
+ *               slot and the workspace may hold anything on entry).  Workgroups of other frames exit at once.
+ *   apply pass  every workgroup adds its frame's partial sums (at most 1024), takes the mean, applies the frame's whole chain to
+ *               its pixels in registers and stores once.
+ * Each lane takes 16 consecutive pixels of the three planes: one 16-byte load / store per plane when H W is a multiple of 16 and
+ * `in` / `out` are 16-byte aligned (planes of another size do not keep the alignment from one plane to the next), 4-byte words
+ * when H W is a multiple of 4 and the pointers are 4-byte aligned, single bytes otherwise and for the last, partial run.
+ * FFB6D_ERR_ARG, with nothing launched or written: negative sizes, a null pointer, in == out, B > 65535;
+ * FFB6D_ERR_WORKSPACE: a workspace below ffb6d_color_jitter_workspace_bytes (or not 8-byte aligned). */
+int ffb6d_color_jitter_u8(const uint8_t* in, const ffb6d_jitter_frame_t* frames, uint8_t* out, int B, int64_t H, int64_t W,
+                          void* workspace, size_t workspace_bytes, ffb6d_stream_t stream);
 
 #ifdef __cplusplus
 }
