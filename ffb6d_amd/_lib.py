@@ -51,6 +51,7 @@ SIGNATURES = {
     "ffb6d_wino4_input_f32": (_i32, [_vp, _vp, _i64, _i64, _i64, _i64, _i64, _vp]),
     "ffb6d_wino4_output_f32": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _i64, _i32, _c.c_float, _vp]),
     "ffb6d_wino4_conv_f32": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _i64, _i32, _c.c_float, _i32, _vp]),
+    "ffb6d_wino4_conv_form": (_i32, [_i64, _i64]),
     "ffb6d_mlp_pm_set_big_form": (None, [_i32]),
     "ffb6d_mlp_pm_set_seq_lin": (None, [_i32]),
     "ffb6d_att_pool_pm_f32": (_i32, [_vp, _vp, _i64, _i64, _vp, _i32, _vp, _i64, _i64, _vp, _i64, _i64, _i64, _i32, _vp]),

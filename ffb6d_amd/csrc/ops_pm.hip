@@ -634,6 +634,8 @@ int ffb6d_wino4_conv_f32(const float* x, const float* u, const float* scale, con
     return wino::conv4_f32(x, u, scale, shift, res, rscale, rshift, out, B, H, W, C, O, act, slope, form, stream);
 }
 
+int ffb6d_wino4_conv_form(int64_t C, int64_t O) { return wino::conv4_form(C, O); }
+
 int ffb6d_affine_relu_maxpool_pm(int dtype, const void* x, const float* scale, const float* shift, void* out, int64_t B, int64_t IH,
                                  int64_t IW, int64_t C, ffb6d_stream_t stream)
 {

@@ -171,7 +171,9 @@ wino_output_f32_kernel(const float* __restrict__ m, const float* __restrict__ sc
 __device__ __forceinline__ float4 operator*(float a, float4 b) { return make_float4(a * b.x, a * b.y, a * b.z, a * b.w); }
 
 // t = B^T s,  B^T = [[2,3,-4,-3,2,0],[0,-2,-5,-1,2,0],[0,2,1,-5,2,0],[0,-1,-2,1,2,0],[0,2,-1,-2,1,0],[0,2,3,-4,-3,2]]
-__device__ __forceinline__ void wino4_bt(const float4 (&s)[6], float4 (&t)[6])
+// (V: float4, or a narrower vector of channels -- the same expression per channel)
+template <typename V>
+__device__ __forceinline__ void wino4_bt(const V (&s)[6], V (&t)[6])
 {
     t[0] = ((2.f * s[0] + 3.f * s[1]) - (4.f * s[2] + 3.f * s[3])) + 2.f * s[4];
     t[1] = (2.f * s[4] - s[3]) - (2.f * s[1] + 5.f * s[2]);

@@ -275,7 +275,7 @@ def wino4_conv(x, u, scale, shift, act=ACT_NONE, slope=0.0, residual=None, res_a
     """3x3 / stride 1 / padding 1 convolution by Winograd F(4x4,3x3) in one launch, with the glue of affine_act_ on the way out
     (csrc/winograd_fused.h): x [B,H,W,C] fp32, u [36,O,C] = forward_pm.wino4_filter(weight) -> [B,H,W,O] = act(scale * conv(x) + shift +
     residual term).  C in WINO4_CONV_CIN, O in WINO4_CONV_COUT.  `out` (contiguous [B,H,W,O]) may alias neither x nor the residual.
-    form: 0 = automatic, 1 / 2 = the kernel's two workgroup shapes (tests, measurements)."""
+    form: 0 = automatic (per width, csrc/winograd_fused.h: conv4_form), 1 / 2 / 3 = the kernel's workgroup shapes (tests, measurements)."""
     _need_gpu(x, u)
     lib = _lib.load()
     if x.dtype != torch.float32 or x.dim() != 4 or not x.is_contiguous():
@@ -303,6 +303,11 @@ def wino4_conv(x, u, scale, shift, act=ACT_NONE, slope=0.0, residual=None, res_a
                                       int(form), _stream(x))
     _lib.check(rc, "ffb6d_wino4_conv_f32")
     return out
+
+
+def wino4_conv_form(C, O):
+    """The workgroup shape wino4_conv(form=0) takes for C input and O output channels (the measured per-width table of the library)."""
+    return int(_lib.load().ffb6d_wino4_conv_form(int(C), int(O)))
 
 
 def att_pool(f, nei_idx, g, w_fc, out=None):

@@ -192,10 +192,13 @@ int ffb6d_wino4_output_f32(const float* m, const float* scale, const float* shif
 /* Winograd F(4x4,3x3) in one launch (csrc/winograd_fused.h), for C in {64, 128} and O in {64, 128, 256}:
  *   out [B,H,W,O] = act(scale * conv3x3(x [B,H,W,C], padding 1) + shift + residual term), the expression of ffb6d_wino4_output_f32,
  * u [36][O][C] the transformed filter of the pair above.  V exists in LDS only, M in registers only.  out may alias neither res nor x;
- * 16-byte aligned pointers; every tensor under 2 GiB.  form: 0 = automatic, 1 / 2 = the two workgroup shapes (tests, measurements). */
+ * 16-byte aligned pointers; every tensor under 2 GiB.  form: 0 = automatic (chosen per width), 1 / 2 / 3 = the workgroup
+ * shapes (tests, measurements); all forms give the same bits. */
 int ffb6d_wino4_conv_f32(const float* x, const float* u, const float* scale, const float* shift, const float* res, const float* rscale,
                          const float* rshift, float* out, int64_t B, int64_t H, int64_t W, int64_t C, int64_t O, int act, float slope,
                          int form, ffb6d_stream_t stream);
+/* the workgroup shape form 0 takes for C input and O output channels */
+int ffb6d_wino4_conv_form(int64_t C, int64_t O);
 
 /* Att_pooling.forward up to the pooled tensor (RandLANet.py:243-248) with the neighbour gather fused in:
  * S[(n,k),:] = [ f[nei[n,k],:] | g[(n,k),:] ], out[n,m] = sum_k S[(n,k),m] * softmax_k((S w_fc^T)[(n,k),m]).

@@ -7,8 +7,9 @@ argv: [B H W] (default 8 60 80: the trunk map of the benchmark) [reps]
 
 argv: narrow [reps] -- the narrow trunk layers instead, (8,120,160,64->64), (8,60,80,128->128) and (8,60,80,128->256): MIOpen's convolution +
 affine_act_ with the pinned find-db as bench.py uses it (device events around the pair, so MIOpen's zero-fill is inside), the unfused F(4x4)
-path where the batched GEMM accepts the shape, and the fused kernel (csrc/winograd_fused.h) in both workgroup shapes; TFLOP/s of the fused
-kernel by the Winograd multiplies, GB/s by x + residual + out.  One JSON line per shape (profiles/winograd_narrow_layers.jsonl)."""
+path where the batched GEMM accepts the shape, and the fused kernel (csrc/winograd_fused.h) in its three workgroup shapes (median of five
+rounds over the forms, with the smallest and largest) and in the automatic per-width choice; TFLOP/s of the fused kernel by the Winograd
+multiplies, GB/s by x + residual + out.  One JSON line per shape (profiles/winograd_narrow_layers.jsonl, winograd_narrow2_layers.jsonl)."""
 import json
 import os
 import sys
@@ -56,9 +57,14 @@ def narrow():
                "direct_conv_affine_us": timed(lambda: ops_pm.affine_act_(forward_pm.conv(x, conv), scale, shift, act=ops.ACT_RELU, residual=res))}
         if forward_pm.wino_ok(conv, x, m=4) or (cin >= 128 and cin % 32 == 0):
             rec["wino4_unfused_total_us"] = timed(lambda: forward_pm.conv_wino(x, conv, scale, shift, residual=res, m=4))
-        for form in (1, 2):
-            rec["fused_form%d_us" % form] = timed(lambda: ops_pm.wino4_conv(x, u4, scale, shift, act=ops.ACT_RELU, residual=res, out=out,
-                                                                             form=form))
+        runs = {form: [] for form in (1, 2, 3)}
+        for _ in range(5):                                 # the forms in turn, five times: median, and the spread a choice has to beat
+            for form in runs:
+                runs[form].append(timed(lambda: ops_pm.wino4_conv(x, u4, scale, shift, act=ops.ACT_RELU, residual=res, out=out, form=form)))
+        for form, t in runs.items():
+            rec["fused_form%d_us" % form] = sorted(t)[2]
+            rec["fused_form%d_min_max_us" % form] = [round(min(t), 3), round(max(t), 3)]
+        rec["auto_form"] = ops_pm.wino4_conv_form(cin, cout)
         rec["fused_us"] = timed(lambda: ops_pm.wino4_conv(x, u4, scale, shift, act=ops.ACT_RELU, residual=res, out=out))
         rec["fused_tflops"] = 2.0 * 36 * T4 * cin * cout / rec["fused_us"] * 1e-6
         rec["fused_frac_of_fp32_mfma_peak"] = rec["fused_tflops"] / PEAK_TFLOPS
