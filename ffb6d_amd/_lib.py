@@ -138,6 +138,12 @@ SIGNATURES = {
     "ffb6d_fps_workspace_bytes": (_sz, [_i32, _i64, _i32]),
     "ffb6d_fps_f32": (_i32, [_vp, _vp, _i32, _i64, _i64, _i32, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "ffb6d_box_info_f32": (_i32, [_vp, _vp, _i32, _i64, _vp, _vp, _vp, _vp]),
+    # include/ffb6d_orb.h
+    "ffb6d_orb_workspace_bytes": (_sz, [_i32, _i32, _i32, _i32]),
+    "ffb6d_orb_detect_u8": (_i32, [_vp, _i32, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "ffb6d_orb_lift_f32": (_i32, [_vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _c.c_float, _c.c_float, _c.c_float, _c.c_float,
+                                  _i32, _vp, _vp, _vp]),
+    "ffb6d_orb_compact_f32": (_i32, [_vp, _vp, _i32, _i32, _i32, _vp, _vp, _vp, _vp]),
     # include/ffb6d_bop.h
     "ffb6d_bop_mssd_mspd_workspace_bytes": (_sz, [_i32, _i64, _i64]),
     "ffb6d_bop_mssd_mspd_f64": (_i32, [_vp, _vp, _i32, _i64, _i64, _vp, _vp, _vp, _i64, _i64, _vp, _vp, _vp, _vp, _i32, _vp, _i32,

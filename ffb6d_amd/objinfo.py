@@ -9,6 +9,13 @@ tests/fps_ref.py is the numpy restatement the kernels are held against, bit for 
     pose.solve_poses(..., info.mesh_kps, info.mesh_ctr, r_lst=info.r_lst)             # device tensors, by class id
     refine.PreparedModels(info.models)
 
+The reference's default keypoints (use_orbfps, common.py:71-73,129-131) are texture-aware: FPS over ORB corners of a few rendered
+views, lifted into the object frame (gen_obj_info.py:119-125, rgbd_rnder_sift_kp3ds.py).  include/ffb6d_orb.h states the detector
+(the published ORB detector in integers -- not OpenCV's bits) and the lift; tests/orb_ref.py restates them:
+
+    info = objinfo.ObjectInfo.from_meshes(meshes, n_keypoints=8)                      # mesh_kps = FPS of the textured points
+    info.n_found                                                                      # i32 [n_cls]: lifted points per class
+
 Everything but ObjectInfo.save_txt enqueues its kernels on the current stream and returns device tensors: nothing is read back
 and the stream is never waited for.  There is no CPU fallback: tensors must live on a GPU.
 """
@@ -20,7 +27,7 @@ import torch
 from . import _lib
 from .evaluate import ModelPoints
 from .ops import _need_gpu, _stream
-from .render import PreparedMeshes
+from .render import MAX_INSTANCES, PreparedMeshes, _prepared, render
 
 FORM = 0               # csrc/fps.hip ffb6d_fps_set_form: 0 = automatic (resident up to its capacity, streaming above), 1 = resident, 2 = streaming
 
@@ -47,7 +54,7 @@ class _Sets:
 
 
 def _sets(points):
-    """A ModelPoints, a PreparedMeshes (its vertices), a device tensor [N,3] or [S,N,3], or host data (numpy / lists, checked
+    """A ModelPoints, a PreparedMeshes (its vertices), a TexturedPoints, a device tensor [N,3] or [S,N,3], or host data (numpy / lists, checked
     for non-finite values and uploaded) of those shapes.  A CPU tensor is refused, as everywhere in the library."""
     s = _Sets()
     s.single = False
@@ -55,6 +62,10 @@ def _sets(points):
         s.pts, s.begin, s.counts = points.pts, points.begin, np.asarray(points.counts, np.int64)
     elif isinstance(points, PreparedMeshes):
         s.pts, s.begin, s.counts = points.verts, points.vert_begin, np.asarray(points.n_verts, np.int64)
+    elif isinstance(points, TexturedPoints):                 # sizes live on the device: the host knows their bound alone
+        s.pts, s.begin, s.counts = points.pts, points.begin, np.full(points.S, points.max_n, np.int64)
+        s.S, s.total, s.max_n, s.device = points.S, int(points.pts.shape[0]), points.max_n, points.pts.device
+        return s
     else:
         if torch.is_tensor(points):
             shape, dtype = tuple(points.shape), points.dtype
@@ -204,6 +215,173 @@ def _model_points(s, n_model_points, start):
     models.begin = torch.from_numpy(np.concatenate([[0], np.cumsum(models.counts)]).astype(np.int64)).to(s.device)
     return models
 
+# ---- texture-aware keypoints: view poses, the ORB detector, the lift (include/ffb6d_orb.h) ---------------------------------------
+SPHERE_SCALE = 0.18 / 0.035        # the camera sphere's radius per object radius (rgbd_rnder_sift_kp3ds.py:148: r / 0.035 * 0.18)
+DEFAULT_K = ((700.0, 0.0, 320.0), (0.0, 700.0, 240.0), (0.0, 0.0, 1.0))              # rgbd_rnder_sift_kp3ds.py:197
+CHUNK_FRAMES = 32                  # frames rendered and searched at a time: their key image and candidate lists stay near 200 MB
+
+
+def _unit_views(n1, n2):
+    """R f64 [V,3,3], t f64 [V,3]: the object -> camera pose of every view for a camera sphere of radius 1.  Restates
+    PoseUtils.CameraPositions, getCameraPose and get_o2c_pose_cv (dataset_tools/utils.py:225-255,353-395) with the identity
+    object pose; the rotations do not depend on the sphere's radius and the translations are proportional to it."""
+    theta = np.linspace(0.1, np.pi, n1 + 1)[:-1]
+    phi = np.linspace(0, 2 * np.pi, n2 + 1)[:-1]
+    flip = np.diag([1.0, -1.0, -1.0])                        # Blender camera -> computer-vision camera
+    Rs, ts = [], []
+    for th in theta:
+        for ph in phi:
+            loc = np.array([np.sin(th) * np.cos(ph), np.sin(th) * np.sin(ph), np.cos(th)])
+            z = loc / np.linalg.norm(loc)
+            x = -np.cross(z, np.array([0.0, 0.0, 1.0]))
+            x = x / np.linalg.norm(x)
+            y = np.cross(z, x)
+            y = y / np.linalg.norm(y)
+            w2b = np.array([x, y, z])                        # the transpose of the camera pose's rotation
+            Rs.append(flip @ w2b)
+            ts.append(flip @ (-1 * w2b @ loc))
+    return np.array(Rs), np.array(ts)
+
+
+def view_poses(radius, n1=3, n2=3):
+    """Object -> camera poses f64 [S,V,3,4] of the V = n1 * n2 views the reference renders an object of bounding-box radius
+    `radius` from (rgbd_rnder_sift_kp3ds.py:138-156): cameras on a sphere of radius `radius * 0.18 / 0.035` looking at the
+    origin, n1 polar angles from 0.1 rad by n2 azimuths.  radius: a number or [S] host values -> a numpy array; a device tensor
+    [S] (box_info's) -> a device tensor, scaled on the device with nothing read back."""
+    n1, n2 = _samples(n1, "n1"), _samples(n2, "n2")
+    R, t = _unit_views(n1, n2)
+    if torch.is_tensor(radius):
+        _need_gpu(radius)
+        dev = radius.device
+        sph = radius.detach().reshape(-1).to(torch.float64) * SPHERE_SCALE
+        poses = torch.empty((sph.shape[0], n1 * n2, 3, 4), dtype=torch.float64, device=dev)
+        poses[..., :3] = torch.from_numpy(R).to(dev)
+        poses[..., 3] = sph[:, None, None] * torch.from_numpy(t).to(dev)
+        return poses
+    sph = np.asarray(radius, np.float64).reshape(-1) * SPHERE_SCALE
+    if not (np.isfinite(sph).all() and (sph >= 0).all()):
+        raise ValueError("radius must be finite and not negative")
+    poses = np.empty((len(sph), n1 * n2, 3, 4))
+    poses[..., :3] = R
+    poses[..., 3] = sph[:, None, None] * t
+    return poses
+
+
+def orb_quotas(n_features=500, n_levels=8):
+    """Keypoints kept per pyramid level, as ORB shares n_features out (in double): i32 [n_levels] host values."""
+    n_features, n_levels = int(n_features), int(n_levels)
+    if n_features < 1 or not 1 <= n_levels <= 8:
+        raise ValueError(f"n_features must be at least 1 and n_levels 1 .. 8, got {n_features}, {n_levels}")
+    f = 1.0 / 1.2
+    n = n_features * (1.0 - f) / (1.0 - f ** n_levels)
+    out, total = [], 0
+    for _ in range(n_levels - 1):
+        out.append(int(round(n)))                            # round half to even
+        total += out[-1]
+        n *= f
+    out.append(max(n_features - total, 0))
+    return np.asarray(out, np.int32)
+
+
+def _detector(n_features, n_levels, fast_threshold, edge):
+    quota = orb_quotas(n_features, n_levels)
+    fast_threshold, edge = int(fast_threshold), int(edge)
+    if not 0 <= fast_threshold <= 255:
+        raise ValueError(f"fast_threshold must be 0 .. 255, got {fast_threshold}")
+    if not 4 <= edge <= 4096:
+        raise ValueError(f"edge must be 4 .. 4096, got {edge}")
+    return quota, int(n_levels), fast_threshold, edge
+
+
+def _orb_detect(rgb, quota, n_levels, fast_threshold, edge):
+    F, _, H, W = (int(v) for v in rgb.shape)
+    Q = int(quota.sum())
+    dev = rgb.device
+    count = torch.empty((F,), dtype=torch.int32, device=dev)
+    kps = torch.empty((F, Q, 5), dtype=torch.int32, device=dev)
+    resp = torch.empty((F, Q), dtype=torch.int64, device=dev)
+    lib = _lib.load()
+    wbytes = lib.ffb6d_orb_workspace_bytes(F, H, W, n_levels)
+    ws = torch.empty((max(wbytes, 1),), dtype=torch.uint8, device=dev)
+    with torch.cuda.device(dev), _lib.traced("orb_detect", 4 * F * H * W, (F, H, W, n_levels)):
+        rc = lib.ffb6d_orb_detect_u8(rgb.data_ptr(), F, H, W, n_levels, fast_threshold, edge, quota.ctypes.data, count.data_ptr(),
+                                     kps.data_ptr(), resp.data_ptr(), ws.data_ptr(), wbytes, _stream(kps))
+    _lib.check(rc, "ffb6d_orb_detect_u8")
+    return count, kps, resp
+
+
+def orb_detect(rgb, n_features=500, n_levels=8, fast_threshold=20, edge=31):
+    """The detector of include/ffb6d_orb.h on rgb u8 [F,3,H,W] frames (render's layout) on the device: FAST-9 corners on a 1.2x
+    pyramid of n_levels levels, strict 8-neighbour maxima above fast_threshold at least `edge` pixels inside a level, ranked by
+    an integer Harris response, the best orb_quotas(n_features, n_levels)[l] of level l kept.  It is the published ORB
+    detector, not OpenCV's implementation: cv2.ORB's keypoints are not reproduced bit for bit.
+    Returns (count i32 [F], kps i32 [F,Q,5] rows (x, y, level, X, Y) with (X, Y) the pixel of the full frame, resp i64 [F,Q]);
+    Q = n_features unless the quotas round above it; rows past count[f] hold -1 / 0.  Nothing is read back."""
+    if not torch.is_tensor(rgb) or rgb.dtype != torch.uint8 or rgb.dim() != 4 or rgb.shape[1] != 3:
+        raise TypeError("rgb must be a uint8 device tensor [F,3,H,W]")
+    _need_gpu(rgb)
+    return _orb_detect(rgb.contiguous(), *_detector(n_features, n_levels, fast_threshold, edge))
+
+
+class TexturedPoints:
+    """The lifted ORB points of S objects in the layout of the C ABI: pts f32 [S*max_n,3] (zeros past the last point), begin i64
+    [S+1] and n_found i32 [S] on the device; max_n = V*Q is the bound the host knows.  farthest_point_sampling takes it."""
+    __slots__ = ("pts", "begin", "n_found", "S", "max_n")
+
+    def __init__(self, pts, begin, n_found, max_n):
+        self.pts, self.begin, self.n_found, self.S, self.max_n = pts, begin, n_found, int(n_found.shape[0]), int(max_n)
+
+
+def textured_points(meshes, K=DEFAULT_K, H=480, W=640, n1=3, n2=3, min_pixels=500, n_features=500, n_levels=8, fast_threshold=20,
+                    edge=31, radius=None):
+    """The texture-aware 3-D points of every class of a mesh set (rgbd_rnder_sift_kp3ds.py:138-166): each object is rendered
+    from view_poses(its box radius, n1, n2) with the intrinsics K (host data [3,3]), orb_detect runs on the frames, and the
+    detected pixels are lifted through the rendered depth into the object frame (include/ffb6d_orb.h states the lift).  A view
+    that shows fewer than min_pixels pixels of the object contributes nothing.  Frames are made and searched CHUNK_FRAMES at a
+    time.  Returns a TexturedPoints by class id (class 0, the background, and classes without faces are empty sets); look at
+    its n_found before trusting what is sampled from it.  Nothing is read back."""
+    meshes = _prepared(meshes)
+    n1, n2 = _samples(n1, "n1"), _samples(n2, "n2")
+    H, W, V, S = int(H), int(W), n1 * n2, meshes.n_cls
+    if V > MAX_INSTANCES:
+        raise ValueError(f"{V} views per object, at most {MAX_INSTANCES}")
+    if torch.is_tensor(K):
+        raise TypeError("K must be host data [3,3]")
+    K = np.asarray(K, np.float64)
+    if K.shape != (3, 3) or not np.isfinite(K).all() or K[0, 0] == 0 or K[1, 1] == 0:
+        raise ValueError("K must be a finite [3,3] matrix with focal lengths that are not zero")
+    quota, n_levels, fast_threshold, edge = _detector(n_features, n_levels, fast_threshold, edge)
+    Q = int(quota.sum())
+    dev = meshes.device
+    if radius is None:
+        radius = box_info(meshes)[2]
+    poses = view_poses(radius, n1, n2)
+    slot_pts = torch.empty((S * V, Q, 3), dtype=torch.float32, device=dev)
+    slot_ok = torch.empty((S * V, Q), dtype=torch.int32, device=dev)
+    lib = _lib.load()
+    step = max(1, min(MAX_INSTANCES, CHUNK_FRAMES) // V)
+    for s0 in range(0, S, step):
+        s1 = min(s0 + step, S)
+        F = (s1 - s0) * V
+        frame_of = torch.arange(F, dtype=torch.int32, device=dev)
+        class_of = torch.arange(s0, s1, dtype=torch.int32, device=dev).repeat_interleave(V)
+        T = poses[s0:s1].reshape(F, 3, 4).contiguous()
+        out = render(meshes, T, frame_of, class_of, K, F, H, W, outputs=("rgb", "depth", "visible"))
+        count, kps, _ = _orb_detect(out["rgb"], quota, n_levels, fast_threshold, edge)
+        with torch.cuda.device(dev), _lib.traced("orb_lift", 20 * F * Q, (F, Q)):
+            rc = lib.ffb6d_orb_lift_f32(kps.data_ptr(), count.data_ptr(), out["depth"].data_ptr(), out["visible"].data_ptr(), T.data_ptr(),
+                                        F, Q, H, W, K[0, 0], K[1, 1], K[0, 2], K[1, 2], int(min_pixels), slot_pts[s0 * V:].data_ptr(),
+                                        slot_ok[s0 * V:].data_ptr(), _stream(kps))
+        _lib.check(rc, "ffb6d_orb_lift_f32")
+    pts = torch.empty((S * V * Q, 3), dtype=torch.float32, device=dev)
+    begin = torch.empty((S + 1,), dtype=torch.int64, device=dev)
+    n_found = torch.empty((S,), dtype=torch.int32, device=dev)
+    with torch.cuda.device(dev), _lib.traced("orb_compact", 32 * S * V * Q, (S, V, Q)):
+        rc = lib.ffb6d_orb_compact_f32(slot_pts.data_ptr(), slot_ok.data_ptr(), S, V, Q, pts.data_ptr(), begin.data_ptr(),
+                                       n_found.data_ptr(), _stream(pts))
+    _lib.check(rc, "ffb6d_orb_compact_f32")
+    return TexturedPoints(pts, begin, n_found, V * Q)
+
 
 class ObjectInfo:
     """What gen_obj_info.py computes per object, for a whole object set at once and by class id (row 0 = the background class
@@ -213,13 +391,17 @@ class ObjectInfo:
       corners f32 [n_cls,8,3], radius f32 [n_cls]; r_lst f32 [n_cls-1] = radius[1:], the reference's r_lst[cls_id - 1];
       kps_idx i32 [n_cls,n_kps]: the keypoints' vertex indices within their class (-1 for an empty class);
       models: an evaluate.ModelPoints of the FPS subset of n_model_points per class (refine.PreparedModels and evaluate take
-        it as it is), None when n_model_points is None."""
+        it as it is), None when n_model_points is None.
+    Built by from_meshes, mesh_kps holds the texture-aware keypoints (the reference's use_orbfps) and kps_idx is None; then also
+      fps_kps f32 [n_cls,n_kps,3]: the plain FPS keypoints of the vertices; n_found i32 [n_cls]: the lifted ORB points per class;
+      textured: the TexturedPoints they were sampled from.  All three are None otherwise."""
 
     def __init__(self, mesh_kps, mesh_ctr, corners, radius, kps_idx=None, models=None):
         self.mesh_kps, self.mesh_ctr, self.corners, self.radius = mesh_kps, mesh_ctr, corners, radius
         self.kps_idx, self.models = kps_idx, models
         self.r_lst = radius[1:]
         self.n_cls, self.n_kps = int(mesh_kps.shape[0]), int(mesh_kps.shape[1])
+        self.fps_kps = self.n_found = self.textured = None
 
     @classmethod
     def from_points(cls, points, n_keypoints=8, n_model_points=None, start="center"):
@@ -237,23 +419,53 @@ class ObjectInfo:
         models = _model_points(s, n_model_points, start) if n_model_points is not None else None
         return cls(kps, ctr, corners, radius, idx, models)
 
+    @classmethod
+    def from_meshes(cls, meshes, n_keypoints=8, n_model_points=None, keypoints="orb_fps", start="center", **views):
+        """Everything from_points gives, with mesh_kps = the FPS of the meshes' textured_points: what gen_obj_info.py writes as
+        <name>_ORB_fps.txt and what use_orbfps selects downstream.  meshes: a render.PreparedMeshes or the list it takes;
+        **views: textured_points' arguments (K, H, W, n1, n2, min_pixels, n_features, n_levels, fast_threshold, edge).
+        keypoints="fps" keeps the vertex keypoints (from_points' result).  The detector is the published ORB detector stated in
+        include/ffb6d_orb.h, not OpenCV's: a checkpoint trained on the reference's keypoint files must keep using those files.
+        A class with no lifted point gets the empty-set result of the FPS rule, zeros -- there is no fallback to the vertex
+        keypoints: look at n_found (a device tensor, nothing is read back here) before using mesh_kps."""
+        if keypoints not in ("orb_fps", "fps"):
+            raise ValueError(f'keypoints must be "orb_fps" or "fps", got {keypoints!r}')
+        meshes = _prepared(meshes)
+        info = cls.from_points(meshes, n_keypoints, n_model_points, start)
+        if keypoints == "fps":
+            return info
+        tex = textured_points(meshes, radius=info.radius, **views)
+        _, kps, _ = _fps(_sets(tex), n_keypoints, start, False)
+        info.fps_kps, info.mesh_kps, info.kps_idx = info.mesh_kps, kps, None
+        info.n_found, info.textured = tex.n_found, tex
+        return info
+
     def save_txt(self, directory, names):
         """Writes <name>_fps.txt, <name>_corners.txt, <name>_center.txt and <name>_radius.txt per class, in the format of
         gen_obj_info.py:98-117 (one point per line, three numbers separated by blanks; the radius alone on its line), so that
         Basic_Utils.get_kps(kp_pth=) / get_ctr(ctr_pth=) read them with np.loadtxt.  names: a list by class id (None = skip
-        the class) or a dict {class id: name}.  The only call here that copies to the host (and waits for the device)."""
+        the class) or a dict {class id: name}.  The only call here that copies to the host (and waits for the device).
+        With texture-aware keypoints (from_meshes) <name>_fps.txt holds the vertex keypoints, and two more files hold mesh_kps:
+        <name>_ORB_fps.txt (gen_obj_info.py:122) and <name>_<n_kps>_kps.txt, the name Basic_Utils.get_kps reads with use_orbfps
+        (common.py:73,131)."""
         if isinstance(names, dict):
             names = [names.get(c) for c in range(self.n_cls)]
         if len(names) != self.n_cls:
             raise ValueError(f"{len(names)} names for {self.n_cls} classes")
         kps, ctr = self.mesh_kps.cpu().numpy(), self.mesh_ctr.cpu().numpy()
+        orb = None
+        if self.fps_kps is not None:
+            orb, kps = kps, self.fps_kps.cpu().numpy()
         corners, radius = self.corners.cpu().numpy(), self.radius.cpu().numpy()
         os.makedirs(directory, exist_ok=True)
         written = []
         for c, name in enumerate(names):
             if name is None:
                 continue
-            for suffix, rows in (("fps", kps[c]), ("corners", corners[c]), ("center", ctr[c][None]), ("radius", radius[c].reshape(1, 1))):
+            files = [("fps", kps[c]), ("corners", corners[c]), ("center", ctr[c][None]), ("radius", radius[c].reshape(1, 1))]
+            if orb is not None:
+                files += [("ORB_fps", orb[c]), (f"{self.n_kps}_kps", orb[c])]
+            for suffix, rows in files:
                 path = os.path.join(directory, f"{name}_{suffix}.txt")
                 with open(path, "w") as of:
                     for row in rows:
