@@ -1,39 +1,50 @@
 // ffb6d_amd/csrc/kabsch.h -- the reflection-corrected least-squares rotation of best_fit_transform
 // (ffb6d/utils/pvn3d_eval_utils_kpls.py:28-61) from a 3x3 cross-covariance, in double, one thread per problem.
 // Shared by the keypoint fit (csrc/pose.hip) and the ICP refinement (csrc/icp.hip): one body, the same bits in both.
+//
+// The singular vectors come from a cyclic one-sided (Hestenes) Jacobi on H itself, never from H^T H: forming H^T H squares the
+// singular values, and once (s2 / s1)^2 nears 2^-53 the second and third right singular vectors mix freely (thin, planar and
+// rod-like point sets).  The one-sided form is backward stable in H: the rotation it returns is that of some H + dH with
+// |dH| ~ 2^-53 s1, i.e. within a few 2^-53 * cond of the exact one, cond = s1 / (s2 + d s3), d = sign det H
+// (tests/test_rigid_fit_cpu.py holds it to ten times what LAPACK's float64 SVD itself reaches against extended precision).
 #pragma once
 #include <hip/hip_runtime.h>
 
 namespace ffb6d {
 
-__device__ inline void jacobi_eigen3(double a[3][3], double v[3][3]) {
+// G = H V with mutually orthogonal columns, V orthogonal: g holds H on entry and U S on exit (columns in no particular order).
+// A pair of columns is rotated while |g_p . g_q| > 1.5 * 2^-52 |g_p| |g_q|; the comparison is false for NaN and for a zero column,
+// and the number of sweeps is bounded, so no input can spin.
+__device__ inline void jacobi_svd3(double g[3][3], double v[3][3]) {
     for (int i = 0; i < 3; ++i)
         for (int j = 0; j < 3; ++j) v[i][j] = i == j;
     for (int sweep = 0; sweep < 30; ++sweep) {
-        const double off = fabs(a[0][1]) + fabs(a[0][2]) + fabs(a[1][2]);
-        if (off < 1e-300) break;
+        bool rotated = false;
         for (int p = 0; p < 2; ++p)
             for (int q = p + 1; q < 3; ++q) {
-                if (fabs(a[p][q]) < 1e-300) continue;
-                const double theta = (a[q][q] - a[p][p]) / (2.0 * a[p][q]);
-                const double tt = (theta >= 0 ? 1.0 : -1.0) / (fabs(theta) + sqrt(theta * theta + 1.0));
-                const double cs = 1.0 / sqrt(tt * tt + 1.0), sn = tt * cs;
-                for (int k = 0; k < 3; ++k) {      // A <- A J
-                    const double akp = a[k][p], akq = a[k][q];
-                    a[k][p] = cs * akp - sn * akq;
-                    a[k][q] = sn * akp + cs * akq;
-                }
-                for (int k = 0; k < 3; ++k) {      // A <- J^T A
-                    const double apk = a[p][k], aqk = a[q][k];
-                    a[p][k] = cs * apk - sn * aqk;
-                    a[q][k] = sn * apk + cs * aqk;
-                }
+                double alpha = 0, beta = 0, gamma = 0;
                 for (int k = 0; k < 3; ++k) {
+                    alpha += g[k][p] * g[k][p];
+                    beta += g[k][q] * g[k][q];
+                    gamma += g[k][p] * g[k][q];
+                }
+                if (!(fabs(gamma) > 0x1.8p-52 * (sqrt(alpha) * sqrt(beta)))) continue;
+                rotated = true;
+                const double zeta = (beta - alpha) / (2.0 * gamma);
+                const double tt = (zeta >= 0 ? 1.0 : -1.0) / (fabs(zeta) + sqrt(zeta * zeta + 1.0));
+                const double cs = 1.0 / sqrt(tt * tt + 1.0), sn = tt * cs;
+                for (int k = 0; k < 3; ++k) {      // G <- G J
+                    const double gkp = g[k][p], gkq = g[k][q];
+                    g[k][p] = cs * gkp - sn * gkq;
+                    g[k][q] = sn * gkp + cs * gkq;
+                }
+                for (int k = 0; k < 3; ++k) {      // V <- V J
                     const double vkp = v[k][p], vkq = v[k][q];
                     v[k][p] = cs * vkp - sn * vkq;
                     v[k][q] = sn * vkp + cs * vkq;
                 }
             }
+        if (!rotated) break;
     }
 }
 
@@ -65,15 +76,17 @@ __device__ inline void any_orthogonal(const double* u, double* o) {
 // [R|t] (row-major double [3,4]) from H = sum (a_i - ca)(b_i - cb)^T and the two centroids: R minimises sum |R (a_i - ca) - (b_i - cb)|^2
 // over the rotations, t = cb - R ca
 __device__ inline void kabsch_from_covariance(const double H[3][3], const double ca[3], const double cb[3], double* out) {
-    // H = U S V^T: eigenvectors of H^T H give V; u_k = H v_k / s_k
-    double M[3][3], V[3][3];
+    // H = U S V^T: one-sided Jacobi gives V and G = H V = U S; s_k = |g_k|, u_k = g_k / s_k
+    double G[3][3], V[3][3];
     for (int r = 0; r < 3; ++r)
-        for (int c = 0; c < 3; ++c) M[r][c] = H[0][r] * H[0][c] + H[1][r] * H[1][c] + H[2][r] * H[2][c];
-    jacobi_eigen3(M, V);
+        for (int c = 0; c < 3; ++c) G[r][c] = H[r][c];
+    jacobi_svd3(G, V);
+    double n2[3];
+    for (int c = 0; c < 3; ++c) n2[c] = G[0][c] * G[0][c] + G[1][c] * G[1][c] + G[2][c] * G[2][c];
     int order[3] = {0, 1, 2};
     for (int i = 0; i < 2; ++i)
         for (int j = i + 1; j < 3; ++j)
-            if (M[order[j]][order[j]] > M[order[i]][order[i]]) {
+            if (n2[order[j]] > n2[order[i]]) {
                 const int tmp = order[i];
                 order[i] = order[j];
                 order[j] = tmp;
@@ -82,16 +95,19 @@ __device__ inline void kabsch_from_covariance(const double H[3][3], const double
     for (int k = 0; k < 3; ++k)
         for (int r = 0; r < 3; ++r) v[k][r] = V[r][order[k]];
     for (int k = 0; k < 2; ++k)
-        for (int r = 0; r < 3; ++r) u[k][r] = H[r][0] * v[k][0] + H[r][1] * v[k][1] + H[r][2] * v[k][2];
+        for (int r = 0; r < 3; ++r) u[k][r] = G[r][order[k]];
     const double s1 = normalize3(u[0]);
     if (!(s1 > 0)) {                           // H = 0: any rotation is optimal, return the identity
         u[0][0] = v[0][0] = 1; u[0][1] = u[0][2] = v[0][1] = v[0][2] = 0;
         u[1][1] = v[1][1] = 1; u[1][0] = u[1][2] = v[1][0] = v[1][2] = 0;
     } else {
+        // rank 1: the plane is free.  A second column below 2^-60 s1 is rounding residue of the rotations (they leave ~2^-53 s1)
+        // and says nothing about u2; choosing u2 freely then costs at most 2 s2 <= 2^-59 s1 of the objective
+        const double s2 = normalize3(u[1]);
         const double proj = u[1][0] * u[0][0] + u[1][1] * u[0][1] + u[1][2] * u[0][2];
         for (int r = 0; r < 3; ++r) u[1][r] -= proj * u[0][r];
-        const double s2 = normalize3(u[1]);
-        if (!(s2 > 1e-12 * s1)) any_orthogonal(u[0], u[1]);   // rank 1: the plane is free
+        const double rest = normalize3(u[1]);
+        if (!(s2 > 0x1p-60 * s1) || !(rest > 0.5)) any_orthogonal(u[0], u[1]);
     }
     // third pair by right-handedness on both sides == the reference's det(R) < 0 correction (:53-56):
     // R = V diag(1, 1, det(V U^T)) U^T does not depend on the sign choice of u3 / v3

@@ -83,7 +83,16 @@ int ffb6d_refine_mask_by_center(const float* pcld, const float* ctr_offsets, con
 
 /* best_fit_transform for P problems (:28-61): T[p] = [R|t] (row-major double [P,3,4]) minimising
  * sum |R*model[p,i] + t - found[p,i]|^2, reflection-corrected.  model/found f32 [P,n,3].
- * Computed in double from the float inputs. */
+ * Computed in double from the float inputs: two-pass centring, H = sum (a_i - c_a)(b_i - c_b)^T = U diag(s1,s2,s3) V^T by a
+ * one-sided Jacobi on H itself (csrc/kabsch.h; H^T H is never formed), R = V diag(1, 1, d) U^T with d = det(V U^T), t = c_b - R c_a.
+ * Accuracy, with cond = s1 / (s2 + d*s3) and against the same fit by a float64 LAPACK SVD (tests/test_rigid_fit_gpu.py):
+ *   - R is orthonormal with det R = +1, and t = c_b - R c_a, to 1e-12, for every finite input;
+ *   - the objective sum |R (a_i - c_a) - (b_i - c_b)|^2 exceeds its minimum by no more than 3.4e-14 * s1 -- thin, planar,
+ *     mirrored and rank-deficient sets (a line, equal points, n <= 2: the rotation is then partly free) included;
+ *   - max |R - R_svd| <= 9.2e-14 * cond wherever cond <= 1e10, which is ten times what the LAPACK fit itself reaches against
+ *     extended precision;
+ *   - H = 0 gives exactly the identity rotation; a problem's result does not depend on the other problems of the call, and
+ *     a problem with NaN or inf input yields non-finite output without affecting the others. */
 int ffb6d_best_fit_transform_f32(const float* model, const float* found, int P, int n, double* T,
                                  ffb6d_stream_t stream);
 

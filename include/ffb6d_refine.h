@@ -12,7 +12,10 @@
  *   3. the pair is kept when d2 <= max_dist * max_dist (float32; a NaN distance is never kept; max_dist = inf keeps all)
  *   4. [R|t] <- the reflection-corrected least-squares transform model[m(i)] -> s_i over the kept pairs, in double from
  *      the float inputs (the arithmetic of ffb6d_best_fit_transform_f32 after the sums; the sums are made per block of
- *      64 scene points and added in block order: no atomics, the same bits in every run)
+ *      64 scene points and added in block order: no atomics, the same bits in every run).  H is formed in one pass,
+ *      H = sum m s^T - n c_a c_b^T, so the accuracy stated for ffb6d_best_fit_transform_f32 holds with cond multiplied by
+ *      (s1 + n |c_a| |c_b|) / s1: max |R - R_svd| <= 9.2e-14 * cond * (s1 + n |c_a| |c_b|) / s1 -- a model cloud given
+ *      about its own centre loses nothing, one given far from its origin loses the cancellation
  *   5. the problem stops after max_iter iterations; earlier when fewer than min_pairs pairs were kept (the pose of
  *      that iteration is left as it is) or, with tol > 0, when the update moved no corner of the model's bounding
  *      box by more than tol metres.

@@ -13,8 +13,10 @@ the same cluster.  Hence:
     labels                <= 0.5 % of a set's points may flip (points on the ball's surface)
     poses [R|t]           <= 5e-3 (9-point Kabsch of keypoints that each carry <= 5e-4 m over a
                           0.2 m model)
-best_fit_transform alone (same keypoints in): the reference runs LAPACK in float32, the kernel
-Jacobi in float64 -> |diff| <= 2e-5.
+best_fit_transform alone (same keypoints in): the reference runs LAPACK in float32, the kernel a
+one-sided Jacobi SVD of H in float64 (csrc/kabsch.h) -> |diff| <= BFT_TOL = 2e-5, the float32
+side's error on these well-spread 9-point sets.  What the float64 side itself guarantees, on thin,
+planar and mirrored sets as well, is held by tests/test_rigid_fit_gpu.py.
 """
 import importlib.util
 import os
