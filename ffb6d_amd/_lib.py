@@ -46,6 +46,10 @@ SIGNATURES = {
     "ffb6d_mlp_pm_choice": (_i32, [_i64, _i64, _i64, _i64, _i32, _i32, _i32]),
     "ffb6d_mlp_pm_seq_plan": (_i32, [_i64, _i64]),
     "ffb6d_mlp_pm_batched_f32": (_i32, [_vp, _i64, _i64, _vp, _i64, _i64, _vp, _i64, _i64, _i64, _i32, _vp]),
+    "ffb6d_mlp_pm_split_w": (_i32, [_vp, _vp, _i64, _vp]),
+    "ffb6d_mlp_pm_split_f32": (_i32, [_vp, _vp, _vp, _i64, _i64, _vp, _i64, _vp, _i64, _i64, _vp, _i64, _vp, _i64, _i32, _i64, _vp,
+                                      _i64, _i64, _i64, _i32, _i32, _vp]),
+    "ffb6d_mlp_pm_split_batched_f32": (_i32, [_vp, _i64, _i64, _vp, _i64, _i64, _vp, _i64, _i64, _i64, _vp]),
     "ffb6d_wino_input_f32": (_i32, [_vp, _vp, _i64, _i64, _i64, _i64, _i64, _vp]),
     "ffb6d_wino_output_f32": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _i64, _i32, _c.c_float, _vp]),
     "ffb6d_wino4_input_f32": (_i32, [_vp, _vp, _i64, _i64, _i64, _i64, _i64, _vp]),

@@ -160,6 +160,29 @@ GEMM_BIG_FORM = True
 # sequences get in the way of the side streams' kernels, as the persistent forms of round 4 did).
 GEMM_SEQ_LIN = False
 GEMM_SEQ_LIN_ONE = False
+# The launches of the tile-sequence form in the split-bf16 form (csrc/mlp_pm_split.hip: every fp32 operand as three bf16 parts, six
+# v_mfma_f32_32x32x16_bf16 products per fragment pair, fp32 accumulation; W pre-split once per weight version).  Asked for explicitly
+# (tile_hint 10): the automatic choice of ops_pm.mlp / mlp_batched is unchanged.  NOT bit-identical to the fp32 MFMA forms: within HOT_TOL,
+# per operator <= 8.2e-7 of range against float64 where the tile-sequence form has <= 2.4e-7 (profiles/split_gemm_accuracy.json).
+# Finite activations and weights only (an inf would become NaN).  Measured alone on the chip (profiles/split_gemm_layers.jsonl): 1.21-1.53 x
+# on every routed layer; the step: profiles/split_gemm_ab.json.
+GEMM_SPLIT_FORM = True
+
+
+def gemm_split_takes(rows, cout, K, act=0):
+    """Which single-source fp32 launches take the split-bf16 form: those the automatic choice sends to the tile-sequence form, inside the
+    range that was measured layer by layer (K 256 .. 1024, cout 256 .. 2304, 38400 rows and more; DESIGN.md section 4a, form 6)."""
+    return GEMM_SPLIT_FORM and K % 32 == 0 and K >= 256 and cout >= 256 and cout % 4 == 0 and rows >= 32768 and 0 <= int(act) <= 2 and \
+        (_lib.load().ffb6d_mlp_pm_choice(rows, cout, K, 0, int(act), 0, 0) & 255) == 8
+
+
+def mlp_long(owner, key, sources, x, w, bias=None, act=ops.ACT_NONE, **kw):
+    """ops_pm.mlp(x, w, bias, act, ...) of a long-row layer: in the split-bf16 form where gemm_split_takes says so, with the three bf16
+    images of w cached on `owner` under the version counters of `sources` (the tensors w was derived from)"""
+    if x.dtype == F32 and gemm_split_takes(x.numel() // x.shape[-1], w.shape[0], w.shape[1], act):
+        w3 = cached(owner, "w3" + key, sources, lambda: ops_pm.split_weight(w))
+        return ops_pm.mlp(x, w, bias, act, tile_hint=ops_pm.SPLIT_FORM, w_split=w3, **kw)
+    return ops_pm.mlp(x, w, bias, act, **kw)
 LFA_WIDTHS = (32, 64, 128, 256)
 
 
@@ -241,7 +264,7 @@ def fusion_step(pre_p2r, fuse_p2r, pre_r2p, fuse_r2p, rgb0, p0, p2r_idx, r2p_idx
     e = mlp(pre_p2r, p0)
     wa, wb, bias = split(fuse_p2r, c, rgb0.dtype)
     y = ops_pm.mlp(e, wb)
-    rgb = ops_pm.mlp(rgb0, wa, bias, fuse_p2r.act_code, gather=(y, p2r_idx.reshape(B, -1)))
+    rgb = mlp_long(fuse_p2r, "p2r%d" % c, mlp_sources(fuse_p2r), rgb0, wa, bias, fuse_p2r.act_code, gather=(y, p2r_idx.reshape(B, -1)))
     with torch.cuda.stream(side):     # r2p: max over the 16 nearest pixels, then conv(cat(p0, pre(.))) as a two-source GEMM
         r2p = mlp(pre_r2p, ops_pm.random_sample(rgb0.view(B, h * w_, c), r2p_idx))
         p = mlp(fuse_r2p, p0, x2=r2p)
@@ -304,6 +327,11 @@ def wino4_weights(c):
     return cached(c, "wino4", [c.weight], lambda: wino4_filter(c.weight))
 
 
+def wino4_split_weights(c):
+    """the three bf16 images of wino4_weights(c) for the split-bf16 form of the batched GEMM, once per weight version"""
+    return cached(c, "wino4_3", [c.weight], lambda: ops_pm.split_weight(wino4_weights(c)))
+
+
 def wino_variant(B, H, W):
     """Output tile edge of the cheaper Winograd variant on a [B,H,W,.] map: 4 iff its GEMM has fewer rows, 36 Tp4 < 16 Tp2 with both
     tile counts padded to 128 (transform traffic follows the same products); a tie stays with F(2x2), and so does everything when
@@ -341,7 +369,11 @@ def conv_wino(x, c, scale, shift, residual=None, res_affine=None, m=None):
         m = wino_variant(*x.shape[:3])
     x = x if x.is_contiguous() else x.contiguous()
     if m == 4:
-        mm = ops_pm.mlp_batched(ops_pm.wino4_input(x), wino4_weights(c))
+        v, u = ops_pm.wino4_input(x), wino4_weights(c)
+        if gemm_split_takes(v.shape[0] * v.shape[1], u.shape[1], u.shape[2]):
+            mm = ops_pm.mlp_batched(v, u, tile_hint=ops_pm.SPLIT_FORM, w_split=wino4_split_weights(c))
+        else:
+            mm = ops_pm.mlp_batched(v, u)
         return ops_pm.wino4_output(mm, x.shape[:3], scale, shift, act=ops.ACT_RELU, residual=residual, res_affine=res_affine)
     if m != 2:
         raise ValueError(f"conv_wino: m must be 2, 4 or None, got {m}")
@@ -435,7 +467,7 @@ def pyramid_pooling(pp, x):
         off += s * s
     prior = ops_pm.psp_prior_sum(torch.cat(zs, dim=1), sizes, (h, w_), dtype=x.dtype)         # [B,h,w,1024]
     wx = cached(pp, "wx%s" % x.dtype, [bw], lambda: wx.to(x.dtype))
-    return ops_pm.mlp(x, wx, pp.bottleneck.bias.detach().float(), ops.ACT_RELU, add=prior, role="cnn")
+    return mlp_long(pp, "wx", [bw], x, wx, pp.bottleneck.bias.detach().float(), ops.ACT_RELU, add=prior, role="cnn")
 
 
 # Which PSPUpsample blocks run in the folded form (csrc/upconv.hip): "auto" = every block in fp32 (measured, profiles/r02_opt_in_forms_ab.json:
@@ -469,8 +501,13 @@ def upconv_folded(ub, dt=F32):
         w = cv.weight.detach() * scale[:, None, None, None]                                  # [cout, cin, 3, 3]
         w9 = w.permute(2, 3, 0, 1).reshape(9 * w.shape[0], w.shape[1])
         return w9.to(dt).contiguous(), shift.float().contiguous(), float(prelu.weight.detach().item())
-    src = [cv.weight, bn.weight, bn.bias, bn.running_mean, bn.running_var, prelu.weight] + ([cv.bias] if cv.bias is not None else [])
-    return cached(ub, "fold9%s" % dt, src, build)
+    return cached(ub, "fold9%s" % dt, upconv_sources(ub), build)
+
+
+def upconv_sources(ub):
+    """the tensors upconv_folded(ub) is derived from"""
+    cv, bn, prelu = ub.conv[1], ub.conv[2], ub.conv[3]
+    return [cv.weight, bn.weight, bn.bias, bn.running_mean, bn.running_var, prelu.weight] + ([cv.bias] if cv.bias is not None else [])
 
 
 def up_block(ub, x):
@@ -483,7 +520,7 @@ def up_block(ub, x):
     if _fold_block(cin, x.dtype) and cv.kernel_size == (3, 3) and cv.padding == (1, 1) \
             and cv.stride == (1, 1) and cv.dilation == (1, 1) and cv.groups == 1:
         w9, shift, slope = upconv_folded(ub, x.dtype)
-        z = ops_pm.mlp(x, w9, role="cnn")                                                     # [B,h,w,9*cout]
+        z = mlp_long(ub, "fold9", upconv_sources(ub), x, w9, role="cnn")                      # [B,h,w,9*cout]
         return ops_pm.upconv_combine(z, shift, slope, (2 * h, 2 * w_))
     y = ops_pm.bilinear_resize(x, (2 * h, 2 * w_), align_corners=True)
     y = conv(y, cv)

@@ -50,7 +50,33 @@ def _sync_big_form(lib):
         _seq_lin_set = MLP_SEQ_LIN
 
 
-def mlp(x1, w, bias=None, act=ACT_NONE, x2=None, add=None, gather=None, x1_gather=None, out=None, tile_hint=0, role="path"):
+def split_weight(w):
+    """w [..., Cout, K] float32 -> [3, ..., Cout, K] bfloat16: the three bf16 parts of every element, w == parts[0] + parts[1] + parts[2]
+    exactly (csrc/mlp_pm_split.hip).  The W operand of the split-bf16 form (mlp / mlp_batched with tile_hint 10); made on the device."""
+    _need_gpu(w)
+    if w.dtype != torch.float32:
+        raise TypeError("split_weight takes a float32 weight")
+    w = w.detach().contiguous()
+    w3 = torch.empty((3,) + tuple(w.shape), dtype=torch.bfloat16, device=w.device)
+    with torch.cuda.device(w.device):
+        rc = _lib.load().ffb6d_mlp_pm_split_w(w.data_ptr(), w3.data_ptr(), w.numel(), _stream(w))
+    _lib.check(rc, "ffb6d_mlp_pm_split_w")
+    return w3
+
+
+SPLIT_FORM = 10                      # tile id of the split-bf16 form (never an automatic choice)
+
+
+def _split_images(w, w_split):
+    if w_split is None:
+        w_split = split_weight(w)
+    if w_split.dtype != torch.bfloat16 or tuple(w_split.shape) != (3,) + tuple(w.shape) or not w_split.is_contiguous():
+        raise ValueError(f"w_split must be contiguous bfloat16 [3, {', '.join(map(str, w.shape))}] (split_weight(w))")
+    return w_split
+
+
+def mlp(x1, w, bias=None, act=ACT_NONE, x2=None, add=None, gather=None, x1_gather=None, out=None, tile_hint=0, role="path",
+        w_split=None):
     """Shared MLP (1x1 conv + folded BatchNorm + activation; pytorch_utils.py:75-129, RandLA/pytorch_utils.py:35-111)
     on row-major activations:  out[r,:] = act(w @ cat(x1[r], x2[r]) + bias + extra[r])
         x1 [..., K1], x2 [..., K2] or None, w [Cout, K1+K2] (conv weight layout, BN folded), bias [Cout] or None
@@ -59,7 +85,8 @@ def mlp(x1, w, bias=None, act=ACT_NONE, x2=None, add=None, gather=None, x1_gathe
         x1_gather = idx [B, P]: x1 is [B, M, K1] and row (b, p) of the GEMM reads x1[b, idx[b, p]]   (`choose`, :309-312)
     act: ACT_NONE / ACT_RELU / ACT_LEAKY / ACT_LOG_SOFTMAX (over the Cout <= 64 channels, pspnet.py:108-112).
     Returns [..., Cout] (or writes `out`, which may be a channel slice of a wider row buffer).
-    `role` only labels the launch in traces (bench.py reports the north-star path's GEMMs and the colour decoder's separately)."""
+    `role` only labels the launch in traces (bench.py reports the north-star path's GEMMs and the colour decoder's separately).
+    tile_hint 10 = the split-bf16 form (fp32 only; csrc/mlp_pm_split.hip) with w_split = split_weight(w) (None: split here)."""
     _need_gpu(x1, w)
     lib = _lib.load()
     _sync_big_form(lib)
@@ -125,6 +152,19 @@ def mlp(x1, w, bias=None, act=ACT_NONE, x2=None, add=None, gather=None, x1_gathe
         tile = (int(tile_hint) if tile_hint > 0 else lib.ffb6d_mlp_pm_choice(rows, Cout, K1, K2, int(act), int(dt), int(xi is not None))) & 255
     else:
         tile = 0
+    if tile_hint == SPLIT_FORM:
+        if dt:
+            raise TypeError("the split-bf16 form (tile_hint 10) takes float32 rows")
+        w3 = _split_images(w, w_split)
+        with torch.cuda.device(x1.device), _lib.traced("mlp_pm", nbytes, (K1 + K2, Cout, rows, tile, dt, role)):
+            rc = lib.ffb6d_mlp_pm_split_f32(w3.data_ptr(), bias.data_ptr() if bias is not None else None,
+                                            a.data_ptr(), K1, ld1, xi.data_ptr() if xi is not None else None, px,
+                                            b.data_ptr() if b is not None else None, K2, ld2,
+                                            y.data_ptr() if y is not None else None, ldy,
+                                            gi.data_ptr() if gi is not None else None, py, bits, P,
+                                            out.data_ptr(), ldo, rows, Cout, int(act), 0, _stream(x1))
+        _lib.check(rc, "ffb6d_mlp_pm_split_f32")
+        return out
     with torch.cuda.device(x1.device), _lib.traced("mlp_pm", nbytes, (K1 + K2, Cout, rows, tile, dt, role)):
         rc = (lib.ffb6d_mlp_pm_bf16 if dt else lib.ffb6d_mlp_pm_f32)(w.data_ptr(), bias.data_ptr() if bias is not None else None,
                                   a.data_ptr(), K1, ld1, xi.data_ptr() if xi is not None else None, px,
@@ -136,11 +176,13 @@ def mlp(x1, w, bias=None, act=ACT_NONE, x2=None, add=None, gather=None, x1_gathe
     return out
 
 
-def mlp_batched(x, w, out=None, tile_hint=0):
+def mlp_batched(x, w, out=None, tile_hint=0, w_split=None, rows=None):
     """One launch for a stack of GEMMs that share their shape: x [G, R, K], w [G, Cout, K] -> out [G, R, Cout], out[g] = x[g] w[g]^T
     (csrc/mlp_pm.hip: ffb6d_mlp_pm_batched_f32 -- the 16 or 36 planes of a Winograd-transformed convolution).  fp32, R a multiple of 128
     (a 128-row tile multiplies one matrix), no bias / activation.  tile_hint 0 = the tile-sequence form (the LDS-tiled form when
-    MLP_SEQ_FORM is off), 7 / 8 + 256 * plan select explicitly.  Every out[g] carries the bits of mlp(x[g], w[g]) in the same form."""
+    MLP_SEQ_FORM is off), 7 / 8 + 256 * plan select explicitly, 10 = the split-bf16 form with w_split = split_weight(w) (None: split
+    here; R a multiple of 128, K of 32).  Every out[g] carries the bits of mlp(x[g], w[g]) in the same form.
+    rows (tile_hint 10 only): multiply the first `rows` of the G * R rows only, the others of `out` stay as they are."""
     _need_gpu(x, w)
     lib = _lib.load()
     if x.dtype != torch.float32 or w.dtype != torch.float32 or (out is not None and out.dtype != torch.float32):
@@ -156,6 +198,17 @@ def mlp_batched(x, w, out=None, tile_hint=0):
     if tile_hint == 0 and not MLP_SEQ_FORM:
         tile_hint = 7
     nbytes = 4 * G * (Cout * K + R * K + R * Cout)
+    if tile_hint == SPLIT_FORM:
+        w3 = _split_images(w, w_split)
+        n_rows = G * R if rows is None else int(rows)
+        if not 0 <= n_rows <= G * R:
+            raise ValueError(f"rows must lie in [0, {G * R}]")
+        with torch.cuda.device(x.device), _lib.traced("mlp_pm_batched", nbytes, (K, Cout, n_rows, SPLIT_FORM, 0, "cnn")):
+            rc = lib.ffb6d_mlp_pm_split_batched_f32(w3.data_ptr(), G, R, x.data_ptr(), K, K, out.data_ptr(), Cout, n_rows, Cout, _stream(x))
+        _lib.check(rc, "ffb6d_mlp_pm_split_batched_f32")
+        return out
+    if rows is not None:
+        raise ValueError("rows is an argument of the split-bf16 form (tile_hint 10)")
     with torch.cuda.device(x.device), _lib.traced("mlp_pm_batched", nbytes, (K, Cout, G * R, (int(tile_hint) & 255) or 8, 0, "cnn")):
         rc = lib.ffb6d_mlp_pm_batched_f32(w.data_ptr(), Cout * K, R, x.data_ptr(), K, K, out.data_ptr(), Cout, G * R, Cout,
                                           int(tile_hint), _stream(x))

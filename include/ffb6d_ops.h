@@ -167,6 +167,25 @@ void ffb6d_mlp_pm_set_big_form(int on);
 int ffb6d_mlp_pm_batched_f32(const float* w, int64_t w_stride, int64_t rows_per_w, const float* x, int64_t k, int64_t ld, float* out,
                              int64_t ldo, int64_t rows, int64_t cout, int tile_hint, ffb6d_stream_t stream);
 
+/* Split-bf16 form of the long-row fp32 GEMMs (csrc/mlp_pm_split.hip; tile id 10 in traces): every fp32 operand is the exact sum of three
+ * bf16 numbers, W x is accumulated in fp32 from the six v_mfma_f32_32x32x16_bf16 products whose parts' indices sum to at most 2, in a
+ * fixed order (per 16 k: (w part, x part) = (0,2), (1,1), (2,0), (0,1), (1,0), (0,0); k ascending) -- results repeat bit for bit and sit
+ * within 2^-23 sum |w||x| of the exact product before accumulation rounding, as exact as the fp32 MFMA forms.  Never chosen
+ * automatically.  FINITE INPUTS ONLY: +-inf in w or x gives NaN, |x| above the largest finite bf16 (3.3895e38) overflows.
+ *   split_w:  w [n] fp32 -> w3 [3][n] bf16, the three parts of every element (made once per weight version; n = cout * k, or
+ *             matrices * cout * k for the batched entry).
+ *   split_f32: the contract of ffb6d_mlp_pm_f32 with w3 in place of w, for what the form takes: one ungathered source (k2 == 0,
+ *             x1_idx == NULL), k1 a multiple of 32 and >= 64, cout a multiple of 4, act 0..2, 16-byte aligned operand rows, every buffer
+ *             under 2 GiB.  Anything else is an error and nothing is launched (out untouched).  variant must be 0.
+ *   split_batched_f32: the contract of ffb6d_mlp_pm_batched_f32; w3 = split_w of the n_w stacked matrices [n_w][cout][k]. */
+int ffb6d_mlp_pm_split_w(const float* w, void* w3, int64_t n, ffb6d_stream_t stream);
+int ffb6d_mlp_pm_split_f32(const void* w3, const float* bias, const float* x1, int64_t k1, int64_t ld1, const void* x1_idx,
+                           int64_t x1_rows_per_frame, const float* x2, int64_t k2, int64_t ld2, const float* y, int64_t ldy,
+                           const void* y_idx, int64_t y_rows_per_frame, int idx_bits, int64_t rows_per_frame, float* out, int64_t ldo,
+                           int64_t rows, int64_t cout, int act, int variant, ffb6d_stream_t stream);
+int ffb6d_mlp_pm_split_batched_f32(const void* w3, int64_t n_w, int64_t rows_per_w, const float* x, int64_t k, int64_t ld, float* out,
+                                   int64_t ldo, int64_t rows, int64_t cout, ffb6d_stream_t stream);
+
 /* Winograd F(2x2,3x3) data transforms around that GEMM (csrc/winograd.h; 3x3 convolution, stride 1, padding 1, fp32).
  * T = B * ceil(H/2) * ceil(W/2) tiles numbered (b, ty, tx); Tp >= T, a multiple of 128; plane xi = 4u + v = position (u, v) of the
  * transformed 4 x 4 tile.  Every tensor must stay under 2 GiB (error otherwise).
