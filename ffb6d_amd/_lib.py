@@ -155,6 +155,12 @@ SIGNATURES = {
     "ffb6d_bop_vsd_workspace_bytes": (_sz, [_i32, _i32, _i32]),
     "ffb6d_bop_vsd_f32": (_i32, [_vp, _vp, _vp, _vp, _vp, _i32, _vp, _i32, _i32, _i32, _vp, _i32, _c.c_float, _vp, _i32, _vp, _vp,
                                  _vp, _sz, _vp]),
+    # include/ffb6d_bop_scene.h
+    "ffb6d_bop_visib_workspace_bytes": (_sz, [_i32, _i32, _i32]),
+    "ffb6d_bop_visib_f32": (_i32, [_vp, _vp, _vp, _i32, _vp, _i32, _i32, _i32, _c.c_float, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "ffb6d_bop_match_check": (_i32, [_vp, _vp, _vp, _vp, _i32, _i64, _i64, _i64, _i32, _i32]),
+    "ffb6d_bop_match_workspace_bytes": (_sz, [_i32, _i32, _i32]),
+    "ffb6d_bop_match_f64": (_i32, [_vp, _vp, _vp, _i32, _i64, _i64, _i64, _vp, _i32, _vp, _vp, _i32, _vp, _vp, _vp, _vp, _sz, _vp]),
 }
 
 _LIB = None

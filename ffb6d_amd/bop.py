@@ -8,12 +8,21 @@ toolkit to port, tests/bop_ref.py is the numpy restatement the kernels are held 
     err, counts = bop.vsd(depth_test, est_RT, gt_RT, class_of, frame_of, K, meshes, diameters)             # [Q, n_tau]
     ev = bop.BOPEval(models, meshes, syms, diameters); ev.add_batch(...); ev.cal_ar()
 
-The distance calls enqueue their kernels on the current stream and return device tensors; nothing is read back.  There is no CPU
-fallback: the errors are computed by the HIP library on a GPU, only the recall arithmetic is plain numpy (like cal_auc).
+BOPEval scores rows that are one estimate against its own ground truth.  A scene with several instances and several scored
+estimates per object goes through the host side of include/ffb6d_bop_scene.h (restated by tests/bop_scene_ref.py):
 
-Out of scope: matching several scored estimates to the ground-truth instances of a frame (every row is one estimate against its
-ground truth; a missing estimate is an infinite error), BOP JSON / CSV input and output, and the datasets' symmetry tables
-(models_info.json): the caller supplies the transforms.
+    info = bop.instance_info(depth_test, gt_RT, gt_class, gt_frame, K, meshes)        # px counts, boxes, visib_fract per instance
+    groups = bop.pair_rows(est_class, est_frame, gt_class, gt_frame)                  # host: (frame, class) groups and their pairs
+    est_gt, gt_est = bop.match(err, score, groups, thr)                               # greedy by score, per error column and threshold
+    ev = bop.BOPSceneEval(models, meshes, syms, diameters); ev.add_batch(...); ev.cal_ar()
+
+The distance, visibility and matching calls enqueue their kernels on the current stream and return device tensors; nothing is
+read back.  There is no CPU fallback: they are computed by the HIP library on a GPU, only the recall arithmetic is plain numpy
+(like cal_auc) and the grouping of pair_rows is host bookkeeping on the ids.
+
+Out of scope: BOP JSON / CSV input and output, the datasets' symmetry tables (models_info.json: the caller supplies the
+transforms), and rendering each distinct pose once for VSD when a group has more than one pair: the E_g x T_g pairs of a group go
+through `vsd` as independent rows, each rendering its two poses again.  Nothing here claims the bytes of the BOP toolkit's files.
 """
 import math
 
@@ -281,6 +290,186 @@ def vsd(depth_test, est_RT, gt_RT, class_of, frame_of, K, meshes, diameters, del
     return err, counts
 
 
+# ---- instance visibility and matching (include/ffb6d_bop_scene.h) -----------------------------------------------------------
+MAX_GROUP = 64                                       # FFB6D_BOP_MAX_GROUP: estimates, and instances, of one (frame, class)
+MAX_MATCH_COLS = MAX_MATCH_THRS = 16
+INFO_INTS = 12                                       # px_count_all, _valid, _visib, _support, bbox_obj xywh, bbox_visib xywh
+
+
+def visib_compare(depth_test, depth_obj, frame_of, K, delta=VSD_DELTA, masks=False, out=None):
+    """The visibility kernel alone, on depth images that exist already: depth_test f32 [B,H,W], depth_obj f32 [Q,H,W] (row q's
+    model rendered alone under its pose), frame_of i32 [Q], K f64 [B,3,3]: contiguous device tensors.  Q <= 65535.
+    -> (info i32 [Q,12], visib_fract f64 [Q], mask_visib u8 [Q,H,W] or None); `out`: that triple, to be written in place (its mask
+    entry decides whether masks are written)."""
+    _need_gpu(depth_test, depth_obj, frame_of, K)
+    for name, t, dt in (("depth_test", depth_test, torch.float32), ("depth_obj", depth_obj, torch.float32), ("frame_of", frame_of, torch.int32),
+                        ("K", K, torch.float64)):
+        if t.dtype != dt or not t.is_contiguous():
+            raise TypeError(f"{name} must be a contiguous {dt} tensor, got {t.dtype}")
+    dev = depth_test.device
+    B, H, W = (int(v) for v in depth_test.shape)
+    Q = int(frame_of.shape[0])
+    if tuple(depth_obj.shape) != (Q, H, W) or tuple(K.shape) != (B, 3, 3):
+        raise ValueError(f"depth_obj {tuple(depth_obj.shape)} / K {tuple(K.shape)} for {Q} rows and depth_test {tuple(depth_test.shape)}")
+    if out is not None:
+        info, fract, mask = out
+    else:
+        info = torch.empty((Q, INFO_INTS), dtype=torch.int32, device=dev)
+        fract = torch.empty((Q,), dtype=torch.float64, device=dev)
+        mask = torch.empty((Q, H, W), dtype=torch.uint8, device=dev) if masks else None
+    lib = _lib.load()
+    wbytes = lib.ffb6d_bop_visib_workspace_bytes(Q, H, W)
+    ws = torch.empty((max(wbytes, 1),), dtype=torch.uint8, device=dev)
+    with torch.cuda.device(dev), _lib.traced("bop_visib", (8 + (mask is not None)) * Q * H * W, (Q, H, W, mask is not None)):
+        rc = lib.ffb6d_bop_visib_f32(depth_test.data_ptr(), depth_obj.data_ptr(), frame_of.data_ptr(), Q, K.data_ptr(), B, H, W, float(delta),
+                                     info.data_ptr(), fract.data_ptr(), mask.data_ptr() if mask is not None else None, ws.data_ptr(),
+                                     wbytes, _stream(ws))
+    _lib.check(rc, "ffb6d_bop_visib_f32")
+    return info, fract, mask
+
+
+def instance_info(depth_test, RT, class_of, frame_of, K, meshes, delta=VSD_DELTA, masks=False, chunk_rows=None):
+    """What BOP publishes per ground-truth instance (scene_gt_info), and the plausibility figures of an estimated pose: each row's
+    model is drawn ALONE under RT[q] through render.render(..., outputs=("depth",)) and compared with the measured depth of its
+    frame by the visibility kernel.  depth_test [B,H,W] metres, RT [Q,3,4], class_of [Q] into `meshes`, frame_of [Q] into depth_test
+    and K ([B,3,3] or [3,3]): host data (uploaded) or device tensors.  One frame per row: 2 * rows_per_chunk(H, W) rows a chunk (or
+    chunk_rows if smaller) under the renderer's two bounds; results do not depend on it.
+    -> dict of device tensors px_count_all, px_count_valid, px_count_visib, px_count_support i32 [Q], visib_fract f64 [Q], bbox_obj,
+    bbox_visib i32 [Q,4] = x, y, w, h (-1 when empty; bbox_obj covers the part of the silhouette inside the frame) and, with masks,
+    mask_visib u8 [Q,H,W].  A row whose frame id is out of range gives counts 0, boxes -1 and a fraction of NaN.  Host class ids out
+    of range are refused; device ids are not read back: such a row is rendered with a clamped class and returned like a bad frame."""
+    meshes = _render._prepared(meshes)
+    dev = meshes.device
+    test = _device_array(depth_test, dev, torch.float32, np.float32)
+    if test.dim() != 3:
+        raise ValueError(f"depth_test must be [B,H,W], got {tuple(test.shape)}")
+    B, H, W = (int(v) for v in test.shape)
+    if not torch.is_tensor(class_of):
+        c = np.asarray(class_of, np.int64).reshape(-1)
+        if len(c) and (c.min() < 0 or c.max() >= meshes.n_cls):
+            raise ValueError(f"class_of outside [0, {meshes.n_cls})")
+    poses = _device_array(RT, dev, torch.float64, np.float64).reshape(-1, 3, 4)
+    _, _, cls, frm, Kd = _rows(poses, poses, class_of, frame_of, K, dev)
+    if Kd.shape[0] == 1 and B > 1:
+        Kd = Kd.expand(B, 3, 3).contiguous()
+    if int(Kd.shape[0]) != B:
+        raise ValueError(f"K must be [3,3] or [{B},3,3], got {tuple(Kd.shape)}")
+    Q = int(cls.shape[0])
+    info = torch.empty((Q, INFO_INTS), dtype=torch.int32, device=dev)
+    fract = torch.empty((Q,), dtype=torch.float64, device=dev)
+    mask = torch.empty((Q, H, W), dtype=torch.uint8, device=dev) if masks else None
+    bad_cls = (cls < 0) | (cls >= meshes.n_cls)
+    drawn = cls.clamp(0, meshes.n_cls - 1)
+    frm = torch.where(bad_cls, torch.full_like(frm, -1), frm)                    # the kernel's bad-frame row: counts 0, boxes -1, NaN
+    full = 2 * rows_per_chunk(H, W) if CHUNK_PIXELS // (H * W) >= 2 else 1
+    step = full if chunk_rows is None else max(1, min(int(chunk_rows), full))
+    for q0 in range(0, Q, step):
+        q1 = min(Q, q0 + step)
+        n = q1 - q0
+        Kq = Kd[frm[q0:q1].clamp(0, B - 1).long()]                               # a frame id out of range renders with some camera: the row is NaN anyway
+        depth = _render.render(meshes, poses[q0:q1], torch.arange(n, dtype=torch.int32, device=dev), drawn[q0:q1], Kq, n, H, W,
+                               outputs=("depth",))["depth"]
+        visib_compare(test, depth, frm[q0:q1].contiguous(), Kd, delta, out=(info[q0:q1], fract[q0:q1], mask[q0:q1] if masks else None))
+    out = dict(px_count_all=info[:, 0], px_count_valid=info[:, 1], px_count_visib=info[:, 2], px_count_support=info[:, 3], visib_fract=fract,
+               bbox_obj=info[:, 4:8], bbox_visib=info[:, 8:12])
+    if masks:
+        out["mask_visib"] = mask
+    return out
+
+
+def pair_rows(est_class, est_frame, gt_class, gt_frame):
+    """Host bookkeeping on the ids: groups the estimates and the ground-truth instances of a test set by (frame, class) -- groups
+    in ascending (frame, class), members in their input order -- and lists every (estimate, instance) pair of every group, ready to
+    feed `mssd_mspd` and `vsd` (est_RT[pair_est], gt_RT[pair_gt], group_class[pair_group], group_frame[pair_group]).
+    Estimates of a (frame, class) without any instance form a group with T_g = 0, instances without an estimate one with E_g = 0.
+    -> dict of numpy arrays: est_begin, gt_begin i32 [G+1], pair_begin i64 [G+1]; group_frame, group_class i64 [G];
+    est_order i64 [Etot] / gt_order i64 [Gtot]: input index of the member at each grouped position (the order of `match`'s score
+    argument and of its outputs' rows); est_group, gt_group i64: the group at each grouped position; pair_est, pair_gt i64 [Npairs]:
+    INPUT indices of each pair's estimate and instance, pair_group i64 [Npairs]."""
+    ec, ef = np.asarray(est_class, np.int64).reshape(-1), np.asarray(est_frame, np.int64).reshape(-1)
+    gc, gf = np.asarray(gt_class, np.int64).reshape(-1), np.asarray(gt_frame, np.int64).reshape(-1)
+    if len(ec) != len(ef) or len(gc) != len(gf):
+        raise ValueError(f"{len(ec)} / {len(ef)} estimate class / frame ids, {len(gc)} / {len(gf)} ground-truth ones")
+    keys = np.unique(np.stack([np.concatenate([ef, gf]), np.concatenate([ec, gc])], 1), axis=0).reshape(-1, 2)      # sorted by (frame, class)
+    G = len(keys)
+    index = {(int(f), int(c)): g for g, (f, c) in enumerate(keys)}
+    eg = np.array([index[(int(f), int(c))] for f, c in zip(ef, ec)], np.int64).reshape(-1)
+    gg = np.array([index[(int(f), int(c))] for f, c in zip(gf, gc)], np.int64).reshape(-1)
+    est_order, gt_order = np.argsort(eg, kind="stable"), np.argsort(gg, kind="stable")
+    E, T = np.bincount(eg, minlength=G), np.bincount(gg, minlength=G)
+    est_begin = np.concatenate([[0], np.cumsum(E)]).astype(np.int32)
+    gt_begin = np.concatenate([[0], np.cumsum(T)]).astype(np.int32)
+    pair_begin = np.concatenate([[0], np.cumsum(E.astype(np.int64) * T)]).astype(np.int64)
+    pair_est, pair_gt, pair_group = np.zeros(int(pair_begin[-1]), np.int64), np.zeros(int(pair_begin[-1]), np.int64), np.zeros(int(pair_begin[-1]), np.int64)
+    for g in range(G):
+        e = est_order[est_begin[g]:est_begin[g + 1]]
+        t = gt_order[gt_begin[g]:gt_begin[g + 1]]
+        pair_est[pair_begin[g]:pair_begin[g + 1]] = np.repeat(e, len(t))
+        pair_gt[pair_begin[g]:pair_begin[g + 1]] = np.tile(t, len(e))
+        pair_group[pair_begin[g]:pair_begin[g + 1]] = g
+    return dict(est_begin=est_begin, gt_begin=gt_begin, pair_begin=pair_begin, group_frame=keys[:, 0].copy(), group_class=keys[:, 1].copy(),
+                est_order=est_order, gt_order=gt_order, est_group=eg[est_order], gt_group=gg[gt_order], pair_est=pair_est, pair_gt=pair_gt,
+                pair_group=pair_group)
+
+
+def _group_tables(groups, dev):
+    """The three begin tables of `groups` on dev, uploaded once per dict and device"""
+    cache = groups.setdefault("_device", {})
+    if dev not in cache:
+        cache[dev] = tuple(torch.from_numpy(np.ascontiguousarray(groups[k], dt)).to(dev)
+                           for k, dt in (("est_begin", np.int32), ("gt_begin", np.int32), ("pair_begin", np.int64)))
+    return cache[dev]
+
+
+def match(err, score, groups, thr, max_ests=None):
+    """Greedy matching of scored estimates to ground-truth instances, the rule of include/ffb6d_bop_scene.h, for every group and
+    every configuration (error column, threshold) in one launch:
+      err f64 [Npairs] or [Npairs, n_col]: the pair rows of `pair_rows` as `mssd_mspd` / `vsd` score them; score f32 [Etot] in the
+      grouped order (score_in[groups["est_order"]]); thr f64 [G] or [G, n_thr] per-group thresholds; max_ests i32 [G] or None: only
+      the best max_ests[g] estimates of a group are considered (0: all).  Host data (uploaded) or device tensors; `groups`: the dict
+      of pair_rows (its begin tables are checked on the host by ffb6d_bop_match_check, then uploaded once and kept in the dict).
+    -> (est_gt i32 [Etot, n_col, n_thr], gt_est i32 [Gtot, n_col, n_thr]) device tensors of LOCAL indices within the group, -1 = none."""
+    est_begin, gt_begin, pair_begin = (np.ascontiguousarray(groups[k], dt) for k, dt in (("est_begin", np.int32), ("gt_begin", np.int32),
+                                                                                       ("pair_begin", np.int64)))
+    G = len(est_begin) - 1
+    if G < 0 or len(gt_begin) != G + 1 or len(pair_begin) != G + 1:
+        raise ValueError(f"begin tables of {len(est_begin)}, {len(gt_begin)} and {len(pair_begin)} entries")
+    Etot, Gtot, Npairs = int(est_begin[-1]), int(gt_begin[-1]), int(pair_begin[-1])
+    shape = lambda x: tuple(x.shape) if torch.is_tensor(x) else np.shape(x)                                                # noqa: E731
+    es, ts = shape(err), shape(thr)
+    es, ts = es + (1,) * (len(es) == 1), ts + (1,) * (len(ts) == 1)
+    if len(es) != 2 or len(ts) != 2 or es[0] != Npairs or ts[0] != G:
+        raise ValueError(f"err {shape(err)} for {Npairs} pairs, thr {shape(thr)} for {G} groups")
+    n_col, n_thr = int(es[1]), int(ts[1])
+    host_max = None
+    if max_ests is not None and not torch.is_tensor(max_ests):
+        host_max = np.ascontiguousarray(np.asarray(max_ests, np.int32).reshape(-1))
+    if max_ests is not None and int(np.prod(shape(max_ests))) != G:
+        raise ValueError(f"max_ests {shape(max_ests)} for {G} groups")
+    lib = _lib.load()                                                            # the host check comes before any upload
+    _lib.check(lib.ffb6d_bop_match_check(est_begin.ctypes.data, gt_begin.ctypes.data, pair_begin.ctypes.data,
+                                         host_max.ctypes.data if host_max is not None else None, G, Etot, Gtot, Npairs, n_col, n_thr),
+               "ffb6d_bop_match_check")
+    dev = err.device if torch.is_tensor(err) and err.is_cuda else torch.device("cuda", torch.cuda.current_device())
+    errd = _device_array(err, dev, torch.float64, np.float64).reshape(Npairs, n_col)
+    thrd = _device_array(thr, dev, torch.float64, np.float64).reshape(G, n_thr)
+    sc = _device_array(score, dev, torch.float32, np.float32).reshape(-1)
+    if int(sc.shape[0]) != Etot:
+        raise ValueError(f"{int(sc.shape[0])} scores for {Etot} estimates")
+    if max_ests is not None:
+        max_ests = _device_array(max_ests, dev, torch.int32, np.int32).reshape(-1)
+    eb, gb, pb = _group_tables(groups, dev)
+    est_gt = torch.empty((Etot, n_col, n_thr), dtype=torch.int32, device=dev)
+    gt_est = torch.empty((Gtot, n_col, n_thr), dtype=torch.int32, device=dev)
+    _need_gpu(est_gt)
+    with torch.cuda.device(dev), _lib.traced("bop_match", 0, (G, Etot, Gtot, n_col, n_thr)):
+        rc = lib.ffb6d_bop_match_f64(eb.data_ptr(), gb.data_ptr(), pb.data_ptr(), G, Etot, Gtot, Npairs, errd.data_ptr(), n_col, sc.data_ptr(),
+                                     thrd.data_ptr(), n_thr, max_ests.data_ptr() if max_ests is not None else None, est_gt.data_ptr(),
+                                     gt_est.data_ptr(), None, 0, _stream(est_gt))
+    _lib.check(rc, "ffb6d_bop_match_f64")
+    return est_gt, gt_est
+
+
 # ---- recall (host, numpy) ---------------------------------------------------------------------------------------------------
 def recall(errors, thresholds):
     """Fraction of (estimate, threshold) pairs with error < threshold.  errors [N] (or [N,k]: k error values per estimate, each
@@ -374,4 +563,110 @@ class BOPEval:
         out = dict(out)
         for k in ("ar", "ar_vsd", "ar_mssd", "ar_mspd", "n"):
             out[k + "_lst"] = [t[k] for t in table]
+        return out
+
+
+class BOPSceneEval:
+    """BOP19 recall of a test run with several ground-truth instances and several scored estimates per (frame, object): the
+    instances' visibility decides which of them are targets (visib_fract >= min_visib), every (estimate, instance) pair of a
+    (frame, class) group is scored by the three error functions, and estimates are matched to instances greedily by score, once
+    per error function and threshold (include/ffb6d_bop_scene.h).  Arguments as BOPEval.  The matchings and the valid mask stay on
+    the device, one set of tensors per batch, until a summary is asked for."""
+
+    def __init__(self, models, meshes, syms, diameters, delta=VSD_DELTA, min_visib=0.1):
+        self.models, self.meshes, self.syms = models, _render._prepared(meshes), syms
+        self.diameters = np.asarray(_numpy(diameters), np.float64).reshape(-1)
+        self.n_cls = models.n_cls
+        if not (self.meshes.n_cls == syms.n_cls == len(self.diameters) == self.n_cls):
+            raise ValueError("models, meshes, syms and diameters must cover the same classes")
+        self.delta, self.min_visib = delta, min_visib
+        self._diam_dev = torch.from_numpy(self.diameters.astype(np.float32)).to(self.meshes.device)
+        self._pending = []
+        self._hits = {k: np.zeros(0, np.int64) for k in ("vsd", "mssd", "mspd")}      # per instance: configurations in which it was matched
+        self._configs = {k: 0 for k in self._hits}
+        self._considered = {k: 0 for k in self._hits}
+        self.cls_ids, self.valid = np.zeros(0, np.int64), np.zeros(0, bool)
+
+    def add_batch(self, depth_test, K, est_RT, est_class, est_frame, est_score, gt_RT, gt_class, gt_frame):
+        """One batch of frames: depth_test [B,H,W], K [B,3,3] or [3,3]; E estimates est_RT [E,3,4] with est_class / est_frame [E]
+        (host ids) and est_score [E], or None for px_count_support / max(px_count_all, 1) of each estimate's render against the
+        measured depth; T ground-truth instances gt_RT [T,3,4], gt_class / gt_frame [T] (host ids).  Each group may hold at most
+        MAX_GROUP = 64 estimates and 64 instances.  max_ests of a group is its number of valid targets (BOP19's rule), computed
+        on the device.
+        -> the batch's matchings: dict(groups: the dict of pair_rows; valid bool [T] and score f32 [E] in grouped order, visib_fract f64
+        [T] in input order; est_gt / gt_est: {"vsd", "mssd", "mspd"} -> the tensors of `match`), device tensors; None without instances."""
+        ec, ef = np.asarray(_numpy(est_class), np.int64).reshape(-1), np.asarray(_numpy(est_frame), np.int64).reshape(-1)
+        gc, gf = np.asarray(_numpy(gt_class), np.int64).reshape(-1), np.asarray(_numpy(gt_frame), np.int64).reshape(-1)
+        for c in (ec, gc):
+            if len(c) and (c.min() < 0 or c.max() >= self.n_cls):
+                raise ValueError(f"class ids outside [0, {self.n_cls})")
+        if len(gc) == 0:
+            return None
+        dev = self.meshes.device
+        W = int(depth_test.shape[-1])
+        est = _device_array(est_RT, dev, torch.float64, np.float64).reshape(-1, 3, 4)
+        gt = _device_array(gt_RT, dev, torch.float64, np.float64).reshape(-1, 3, 4)
+        groups = pair_rows(ec, ef, gc, gf)
+        idx = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)                                                   # noqa: E731
+        fract = instance_info(depth_test, gt, gc, gf, K, self.meshes, self.delta)["visib_fract"]
+        valid = fract[idx(groups["gt_order"])] >= self.min_visib                                                            # grouped order; NaN: not a target
+        if est_score is None:
+            info = instance_info(depth_test, est, ec, ef, K, self.meshes, self.delta)
+            score = (info["px_count_support"].double() / info["px_count_all"].clamp(min=1).double()).float()
+        else:
+            score = _device_array(est_score, dev, torch.float32, np.float32).reshape(-1)
+        score = score[idx(groups["est_order"])]
+        total = torch.cat([torch.zeros(1, dtype=torch.int64, device=dev), torch.cumsum(valid.long(), 0)])
+        gb = idx(groups["gt_begin"].astype(np.int64))
+        n_valid = (total[gb[1:]] - total[gb[:-1]]).int()                                                                    # valid targets per group
+        E = idx(np.diff(groups["est_begin"]).astype(np.int32))
+        considered = torch.minimum(E, n_valid).sum()                                                                        # a group without targets considers nothing
+        pe, pg = idx(groups["pair_est"]), idx(groups["pair_gt"])
+        pcls, pfrm = groups["group_class"][groups["pair_group"]], groups["group_frame"][groups["pair_group"]]
+        mssd, mspd = mssd_mspd(est[pe], gt[pg], pcls, pfrm, K, self.models, self.syms)
+        err, _ = vsd(depth_test, est[pe], gt[pg], pcls, pfrm, K, self.meshes, self._diam_dev, self.delta, VSD_TAUS)
+        G = len(groups["group_class"])
+        thr = dict(mssd=self.diameters[groups["group_class"]][:, None] * MSSD_THRESHOLDS[None, :],
+                   mspd=(np.full(G, float(W)) / 640.0)[:, None] * MSPD_THRESHOLDS[None, :].astype(np.float64),
+                   vsd=np.broadcast_to(np.asarray(VSD_THRESHOLDS, np.float64)[None, :], (G, len(VSD_THRESHOLDS))))
+        matched = {k: match(e, score, groups, thr[k], n_valid) for k, e in (("vsd", err), ("mssd", mssd), ("mspd", mspd))}
+        gt_est = {k: m[1] for k, m in matched.items()}
+        self._pending.append((gc[groups["gt_order"]], valid, considered, gt_est))
+        return dict(groups=groups, valid=valid, visib_fract=fract, score=score, est_gt={k: m[0] for k, m in matched.items()}, gt_est=gt_est)
+
+    def _flush(self):
+        for cls, valid, considered, gt_est in self._pending:
+            v = valid.cpu().numpy()
+            self.cls_ids, self.valid = np.concatenate([self.cls_ids, cls]), np.concatenate([self.valid, v])
+            for k, m in gt_est.items():
+                n_cfg = int(m.shape[1] * m.shape[2])
+                if self._configs[k] not in (0, n_cfg):
+                    raise ValueError(f"{k}: batches of {self._configs[k]} and {n_cfg} configurations")
+                self._configs[k] = n_cfg
+                self._hits[k] = np.concatenate([self._hits[k], (m >= 0).sum((1, 2)).cpu().numpy().astype(np.int64)])
+                self._considered[k] += int(considered) * n_cfg
+        self._pending = []
+
+    def _recalls(self, sel):
+        n = int(sel.sum())
+        out = {"ar_" + k: (float(self._hits[k][sel].sum()) / float(self._configs[k] * n) if n else 0.0) for k in ("vsd", "mssd", "mspd")}
+        out.update(ar=(out["ar_vsd"] + out["ar_mssd"] + out["ar_mspd"]) / 3.0, n=n)
+        return out
+
+    def cal_ar(self):
+        """-> the dict of BOPEval.cal_ar (ar, ar_vsd, ar_mssd, ar_mspd, n and their per-class `_lst` forms, index 0 = all objects),
+        every recall pooled: the matched valid targets summed over the configurations (10 x 10 for VSD, 10 for MSSD and MSPD),
+        divided by (configurations x valid targets); n counts the valid targets.  With one estimate per instance and every instance
+        valid this is BOPEval.cal_ar() of the same rows exactly.  Also n_targets, n_ignored (instances below min_visib) and, per
+        error function, precision_* = matched valid targets / considered estimates (min(E_g, valid targets of g), summed over the
+        groups and configurations: a match to an ignored instance counts on neither side)."""
+        self._flush()
+        out = self._recalls(self.valid)
+        table = [out] + [self._recalls(self.valid & (self.cls_ids == c)) for c in range(1, self.n_cls)]
+        out = dict(out)
+        for k in ("ar", "ar_vsd", "ar_mssd", "ar_mspd", "n"):
+            out[k + "_lst"] = [t[k] for t in table]
+        out.update(n_targets=int(self.valid.sum()), n_ignored=int((~self.valid).sum()))
+        for k in ("vsd", "mssd", "mspd"):
+            out["precision_" + k] = float(self._hits[k][self.valid].sum()) / float(self._considered[k]) if self._considered[k] else 0.0
         return out

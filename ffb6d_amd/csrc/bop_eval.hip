@@ -21,19 +21,16 @@
 #include <cfloat>
 #include <climits>
 
-#include "common.h"
+#include "bop_common.h"
 #include "ffb6d_bop.h"
 
 namespace {
 
-constexpr int kThreads = 256;
-constexpr int kWaves = kThreads / 64;
+using namespace ffb6d::bop;                         // the run of pixels, Camera, ray_dist, load_px, aligned: shared with bop_scene.hip
+
 constexpr int kSymBlock = 8;                        // symmetries per workgroup: 16 running maxima per thread
 constexpr int kPer = 4;                             // points per thread
 constexpr int kChunk = kThreads * kPer;             // points per workgroup
-constexpr int kPx = 4;                              // pixels per lane and step: 16 bytes of each image
-constexpr int kSteps = 4;
-constexpr int kRunPx = kThreads * kPx * kSteps;     // pixels per workgroup
 constexpr int kCounters = 2 + FFB6D_BOP_MAX_TAUS;
 
 __device__ __forceinline__ int64_t clamp64(int64_t v, int64_t lo, int64_t hi) { return v < lo ? lo : v > hi ? hi : v; }
@@ -240,28 +237,7 @@ __global__ __launch_bounds__(64) void sym_min_kernel(Tables t, int n_chunks, int
 
 // ---- VSD ----------------------------------------------------------------------------------------------------------------------
 
-struct Camera { float fx, fy, cx, cy; };
-
-__device__ __forceinline__ float ray_dist(float z, int r, int c, const Camera& k)
-{
-    if (z == 0.f) return 0.f;
-    const float X = ((static_cast<float>(c) - k.cx) * z) / k.fx;
-    const float Y = ((static_cast<float>(r) - k.cy) * z) / k.fy;
-    return __fsqrt_rn((X * X + Y * Y) + z * z);
-}
-
-// n floats from p (n == kPx and kVec == 4: one 16-byte access); entries past n read as 0
-template <int kVec>
-__device__ __forceinline__ void load_px(const float* __restrict__ p, int n, float (&v)[kPx])
-{
-    if (kVec == 4 && n == kPx) {
-        const float4 x = *reinterpret_cast<const float4*>(p);
-        v[0] = x.x; v[1] = x.y; v[2] = x.z; v[3] = x.w;
-    } else {
-#pragma unroll
-        for (int j = 0; j < kPx; ++j) v[j] = j < n ? p[j] : 0.f;
-    }
-}
+// Camera, ray_dist and load_px: csrc/bop_common.h
 
 __device__ __forceinline__ bool vsd_row_ok(const int* class_of, const int* frame_of, int q, int n_cls, int B)
 {
@@ -378,8 +354,6 @@ __global__ __launch_bounds__(64) void vsd_finish_kernel(const int* __restrict__ 
         }
     }
 }
-
-bool aligned(const void* p, uintptr_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) == 0; }
 
 inline int64_t sym_pad(int64_t max_syms) { return ffb6d::ceil_div(max_syms > 0 ? max_syms : 1, kSymBlock) * kSymBlock; }
 
