@@ -116,6 +116,17 @@ __device__ __forceinline__ void lds_dma_wait()
 #endif
 }
 
+// ... and until every LDS operation of this wave has completed (lgkmcnt(0)): what a wave needs in front of a bare s_barrier that
+// publishes its LDS-DMA pieces and ds_writes while younger requests stay in flight (__syncthreads() would wait for vmcnt(0))
+template <int N>
+__device__ __forceinline__ void ring_wait()
+{
+    static_assert(N >= 0 && N < 64, "vmcnt is a 6-bit counter");
+#if defined(__HIP_DEVICE_COMPILE__)
+    __builtin_amdgcn_s_waitcnt((N & 15) | ((N >> 4) << 14) | 0x0070);      // vmcnt(N) lgkmcnt(0), expcnt left alone (gfx9 encoding)
+#endif
+}
+
 // an integer the compiler cannot see through: what is computed from the result is computed HERE (not hoisted out of the enclosing loop,
 // where it would hold registers across the whole loop)
 __device__ __forceinline__ int opaque(int v)

@@ -24,9 +24,14 @@
 //   * image rows are 64 bytes (4 chunks of 16); LDS chunk c of row r holds the row's chunk c ^ ((r >> 3) & 3): the sixteen lanes a
 //     ds_read_b128 serves per cycle (rows {0-3, 12-15, 20-27} / {4-11, 16-19, 28-31} of a 32-row fragment) then hit sixteen
 //     different 16-byte bank groups (four rows fill a 256-byte bank row; r >> 3 differs between the four row quads of a group);
-//   * two stages of 72 KB: step s + 1 is requested / loaded while step s is multiplied, one barrier per step.
+//   * a ring of two 72 KB slots, one barrier per step; W(s + 1) is requested piece by piece between the MFMAs of step s, X travels
+//     one step further ahead in registers (loaded in step s - 1, split and written in step s, multiplied in step s + 1), and every
+//     wait is counted: none waits for a request younger than the one it needs (the loop's comment has the sequence).
+//     A ring of four 16-k slots, requested three half-steps ahead, was measured and dropped: its barrier per 24 MFMAs cost more
+//     (3-10 % per launch) than its longer cover gained (profiles/split_ring_forms.jsonl; DESIGN.md 4a form 6 has what is and is not measured).
 // XCD-aware order as the other long-row forms: all channel tiles of a point tile on one XCD.  Epilogue: pm_epilogue (fp32).
 #include <algorithm>
+#include <type_traits>
 
 #include "common.h"
 #include "ffb6d_ops.h"
@@ -37,13 +42,18 @@ namespace pm {
 namespace {
 
 constexpr int SP_BLK = 512;
-constexpr int SP_RB = 64;                             // bytes of an image row per step (32 k of bf16)
+constexpr int SP_KS = 32;                             // k of a ring slot = of a loop iteration
+constexpr int SP_RB = 2 * SP_KS;                      // bytes of an image row per slot (bf16)
 constexpr int SP_WIMG = 256 * SP_RB;                  // one W part: 256 channels
 constexpr int SP_XIMG = 128 * SP_RB;                  // one X part: 128 points
 constexpr int SP_XBASE = 3 * SP_WIMG;
-constexpr int SP_STAGE = 3 * SP_WIMG + 3 * SP_XIMG;   // 72 KB
-constexpr int SP_LDS = 2 * SP_STAGE;
+constexpr int SP_SLOT = 3 * SP_WIMG + 3 * SP_XIMG;
+constexpr int SP_NS = 2;                              // slots of the ring
+constexpr int SP_LDS = SP_NS * SP_SLOT;               // 144 KB
 static_assert(SP_LDS <= 160 * 1024, "LDS layout");
+constexpr int SP_NW = 6;                              // LDS-DMA instructions (1 KB each) per wave and slot: 3 parts x 2 halves
+constexpr int SP_NV = 2;                              // 16-byte X loads per thread and slot
+constexpr int SP_NOP = SP_NW + SP_NV;                 // vector-memory operations a wave issues per loop iteration
 
 typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
 
@@ -74,7 +84,7 @@ __global__ void __launch_bounds__(SP_BLK)
 mlp_pm_split_kernel(const PmParams p, const unsigned part_bytes)
 {
     constexpr int OOB = 0x7ffffff0;
-    extern __shared__ __attribute__((aligned(16))) unsigned char lds[];      // [2 stages][W0 | W1 | W2 | X0 | X1 | X2]
+    extern __shared__ __attribute__((aligned(16))) unsigned char lds[];      // [SP_NS slots][W0 | W1 | W2 | X0 | X1 | X2]
 
     const int t = blockIdx.x;
     const int xcd = t & 7, sl = t >> 3;
@@ -88,7 +98,7 @@ mlp_pm_split_kernel(const PmParams p, const unsigned part_bytes)
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int wm = wave >> 2, wn = wave & 3;
     const int K = p.k1;
-    const int nstep = K / 32;                         // at least two (launcher)
+    const int nslot = K / SP_KS;                      // at least SP_NS (launcher: K >= 64)
     const int wrow0 = p.rows_per_w ? (r0 / p.rows_per_w) * p.cout : 0;        // the tile's matrix: its first row in the images
 
     const unsigned char* w3 = static_cast<const unsigned char*>(p.w);
@@ -106,49 +116,60 @@ mlp_pm_split_kernel(const PmParams p, const unsigned part_bytes)
         const int ch = c0 + 128 * h + lrow;
         w_off[h] = ch < p.cout ? (wrow0 + ch) * (K * 2) + lchunk : OOB;
     }
-    auto request_w = [&](int s, int stage) {
-        unsigned char* wi = lds + stage * SP_STAGE + wave * (16 * SP_RB);
+    // slot j of the K range into ring slot rs; past the end of K (j >= nslot) the same number of operations is issued, all lanes out
+    // of range (zeros land in a free ring slot): the counted waits below count operations, so every iteration must issue the same ones
+    auto request_w = [&](int j, int rs, int q0 = 0, int q1 = SP_NW) {         // pieces q0 .. q1 - 1 of the wave's six
+        const bool in = j < nslot;
+        const int so = in ? j * SP_RB : 0;
+        unsigned char* wi = lds + rs * SP_SLOT + wave * (16 * SP_RB);
 #pragma unroll
         for (int pi = 0; pi < 3; ++pi)
 #pragma unroll
-            for (int h = 0; h < 2; ++h) lds_dma16(rs_w[pi], wi + pi * SP_WIMG + h * (128 * SP_RB), w_off[h], s * SP_RB);
+            for (int h = 0; h < 2; ++h)
+                if (pi * 2 + h >= q0 && pi * 2 + h < q1)
+                    lds_dma16(rs_w[pi], wi + pi * SP_WIMG + h * (128 * SP_RB), in ? w_off[h] : OOB, so);
     };
 
-    // X loader: thread -> point row tid >> 2, floats 8 (tid & 3) .. + 7 of the step's 32 = chunk tid & 3 of the row's three images
+    // X loader: thread -> point row tid >> 2, floats 8 (tid & 3) .. + 7 of the slot's 32 = chunk tid & 3 of the row's three images
     const int xrow = threadIdx.x >> 2, xq = threadIdx.x & 3;
     const bool xlive = r0 + xrow < p.rows;
-    const int x_off0 = xlive ? (r0 + xrow) * p.ld1 * 4 + xq * 32 : OOB;
-    const int x_off1 = xlive ? x_off0 + 16 : OOB;
+    int x_off[SP_NV];
+#pragma unroll
+    for (int q = 0; q < SP_NV; ++q) x_off[q] = xlive ? (r0 + xrow) * p.ld1 * 4 + xq * 32 + 16 * q : OOB;
     const int x_dst = SP_XBASE + xrow * SP_RB + ((xq ^ ((xrow >> 3) & 3)) * 16);
-    auto load_x = [&](int s, u32x4 (&v)[2]) {
-        v[0] = __builtin_amdgcn_raw_buffer_load_b128(rs_x, x_off0, s * 128, 0);
-        v[1] = __builtin_amdgcn_raw_buffer_load_b128(rs_x, x_off1, s * 128, 0);
+    auto load_x = [&](int j, u32x4 (&v)[SP_NV]) {
+        const bool in = j < nslot;
+        const int so = in ? j * (SP_KS * 4) : 0;
+#pragma unroll
+        for (int q = 0; q < SP_NV; ++q) v[q] = __builtin_amdgcn_raw_buffer_load_b128(rs_x, in ? x_off[q] : OOB, so, 0);
     };
-    auto write_x = [&](int stage, const u32x4 (&v)[2]) {
-        u32x4 o[3];
+    // pair q (floats 2 q, 2 q + 1 of the thread's eight) of the three images' words
+    auto split_pair = [&](const u32x4 (&v)[SP_NV], int q, unsigned (&o)[3][4]) {
         if constexpr (VAR & 1) {
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                const unsigned pk = (v[q >> 1][2 * (q & 1)] >> 16) | (v[q >> 1][2 * (q & 1) + 1] & 0xffff0000u);
-                o[0][q] = pk; o[1][q] = 0u; o[2][q] = 0u;
-            }
+            o[0][q] = (v[q >> 1][2 * (q & 1)] >> 16) | (v[q >> 1][2 * (q & 1) + 1] & 0xffff0000u);
+            o[1][q] = 0u; o[2][q] = 0u;
         } else {
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                bf16x2 b0, b1, b2;
-                __bf16 s0, s1, s2;
-                split3(__uint_as_float(v[q >> 1][2 * (q & 1)]), s0, s1, s2);
-                b0[0] = s0; b1[0] = s1; b2[0] = s2;
-                split3(__uint_as_float(v[q >> 1][2 * (q & 1) + 1]), s0, s1, s2);
-                b0[1] = s0; b1[1] = s1; b2[1] = s2;
-                o[0][q] = __builtin_bit_cast(unsigned, b0);
-                o[1][q] = __builtin_bit_cast(unsigned, b1);
-                o[2][q] = __builtin_bit_cast(unsigned, b2);
-            }
+            bf16x2 b0, b1, b2;
+            __bf16 s0, s1, s2;
+            split3(__uint_as_float(v[q >> 1][2 * (q & 1)]), s0, s1, s2);
+            b0[0] = s0; b1[0] = s1; b2[0] = s2;
+            split3(__uint_as_float(v[q >> 1][2 * (q & 1) + 1]), s0, s1, s2);
+            b0[1] = s0; b1[1] = s1; b2[1] = s2;
+            o[0][q] = __builtin_bit_cast(unsigned, b0);
+            o[1][q] = __builtin_bit_cast(unsigned, b1);
+            o[2][q] = __builtin_bit_cast(unsigned, b2);
         }
-        unsigned char* xi = lds + stage * SP_STAGE + x_dst;
+    };
+    auto store_x = [&](int rs, const unsigned (&o)[3][4]) {
+        unsigned char* xi = lds + rs * SP_SLOT + x_dst;
 #pragma unroll
-        for (int pj = 0; pj < 3; ++pj) *reinterpret_cast<u32x4*>(xi + pj * SP_XIMG) = o[pj];
+        for (int pj = 0; pj < 3; ++pj) *reinterpret_cast<u32x4*>(xi + pj * SP_XIMG) = u32x4{o[pj][0], o[pj][1], o[pj][2], o[pj][3]};
+    };
+    auto write_x = [&](int rs, const u32x4 (&v)[SP_NV]) {
+        unsigned o[3][4];
+#pragma unroll
+        for (int q = 0; q < 4; ++q) split_pair(v, q, o);
+        store_x(rs, o);
     };
 
     // fragment reads: lane l31 of a 32-row MFMA tile reads chunk 2 ks + kh of its row = LDS chunk (2 ks + kh) ^ ((l31 >> 3) & 3)
@@ -161,58 +182,130 @@ mlp_pm_split_kernel(const PmParams p, const unsigned part_bytes)
 #pragma unroll
         for (int r = 0; r < 16; ++r) acc[i][0][r] = 0.f;
 
-    auto multiply = [&](int stage, int ks) {          // one k16 sub-step: 15 fragment reads, 24 MFMAs per wave
-        const unsigned char* im = lds + stage * SP_STAGE;
+    // reads q0 .. q1 - 1 of the 15 fragment reads of a k16 sub-step, in the order the terms first need them: group g = X part 2 - g,
+    // then the four tiles of W part g (term g multiplies exactly these; terms 3-5 use them again)
+    auto frags = [&](int rs, int ks, u32x4 (&a)[3][4], u32x4 (&b)[3], int q0 = 0, int q1 = 15) {
+        const unsigned char* im = lds + rs * SP_SLOT;
         const int fo = ((2 * ks + kh) ^ fsw) * 16;
-        u32x4 a[3][4], b[3];
 #pragma unroll
-        for (int pj = 0; pj < 3; ++pj) b[pj] = *reinterpret_cast<const u32x4*>(im + b_row + pj * SP_XIMG + fo);
+        for (int g = 0; g < 3; ++g) {
+            if (5 * g >= q0 && 5 * g < q1) b[2 - g] = *reinterpret_cast<const u32x4*>(im + b_row + (2 - g) * SP_XIMG + fo);
 #pragma unroll
-        for (int pi = 0; pi < 3; ++pi)
-#pragma unroll
-            for (int i = 0; i < 4; ++i) a[pi][i] = *reinterpret_cast<const u32x4*>(im + pi * SP_WIMG + a_row + i * (32 * SP_RB) + fo);
+            for (int i = 0; i < 4; ++i)
+                if (5 * g + 1 + i >= q0 && 5 * g + 1 + i < q1)
+                    a[g][i] = *reinterpret_cast<const u32x4*>(im + g * SP_WIMG + a_row + i * (32 * SP_RB) + fo);
+        }
+    };
+    // terms t0 .. t1 - 1 of a k16 sub-step's six (24 MFMAs per wave): small terms first; the four tiles of a term are independent MFMAs
+    auto mma = [&](const u32x4 (&a)[3][4], const u32x4 (&b)[3], int t0, int t1) {
         if constexpr (VAR & 2) {
+            if (t0 == 0) {
 #pragma unroll
-            for (int pi = 0; pi < 3; ++pi)
+                for (int pi = 0; pi < 3; ++pi)
 #pragma unroll
-                for (int i = 0; i < 4; ++i) use_here(a[pi][i][0] ^ b[pi][3]);
+                    for (int i = 0; i < 4; ++i) use_here(a[pi][i][0] ^ b[pi][3]);
+            }
             return;
         }
-        // small terms first; the four tiles of a term are independent MFMAs
         constexpr int TW[6] = {0, 1, 2, 0, 1, 0}, TX[6] = {2, 1, 0, 1, 0, 0};
 #pragma unroll
-        for (int tm = 0; tm < 6; ++tm)
+        for (int tm = 0; tm < 6; ++tm) {
+            if (tm < t0 || tm >= t1) continue;
 #pragma unroll
             for (int i = 0; i < 4; ++i)
                 acc[i][0] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, a[TW[tm]][i]),
                                                                    __builtin_bit_cast(bf16x8, b[TX[tm]]), acc[i][0], 0, 0, 0);
+        }
     };
 
-    {
-        u32x4 xv[2];
-        request_w(0, 0);
-        load_x(0, xv);
-        write_x(0, xv);
+    // The ring.  Step j (32 k) lives in ring slot j & 1.  At the top of iteration h: W(h) and X(h) are in LDS and published, the
+    // registers xr hold (or wait for) X(h + 1).  Iteration h, per wave:
+    //   15 ds_read_b128 of sub-step 0, in term order
+    //   six times: 4 MFMAs of a term | one piece of W(h + 1) into the slot iteration h - 1 read (freed by its barrier) | 2-3 fragment
+    //              reads of sub-step 1                                                                            6 vm operations
+    //   the two loads of X(h + 2) into the registers X(h) left                                                    2 vm operations
+    //   s_waitcnt vmcnt(8): X(h + 1), loaded one iteration ago -- the eight operations issued since stay in flight
+    //   four times: 4 MFMAs of a term of sub-step 1 with the split of a pair of X(h + 1) between them; 4 MFMAs, the three ds_write_b128
+    //              of X(h + 1) into slot (h + 1) & 1; 4 MFMAs
+    //   s_waitcnt vmcnt(2) lgkmcnt(0): the wave's own pieces of W(h + 1) have landed (the loads of X(h + 2) are younger and stay in
+    //              flight), its writes of X(h + 1) are done, its fragment reads of slot h returned before the MFMAs
+    //   s_barrier: slot (h + 1) & 1 is published, slot h & 1 is free.
+    // The main loop holds no other vector-memory wait (checked in the compiled loop: vmcnt(8) / vmcnt(2) only).  Past the end of K the
+    // same operations are issued out of range (zeros, into a free slot): the waits count operations.  The half turn behind the loop
+    // (K % 64 == 32) is the tile's last step: everything it requests is past the end of K, the compiler drops its dead X loads and
+    // places smaller counts of its own for the register uses, and its vmcnt(2) may leave dead W pieces (zeros into the free slot) in
+    // flight.  Nothing reads what it requests, and the vmcnt(0) behind it keeps those pieces from landing after the wave has ended.
+    constexpr int WAIT_X = (SP_NS - 1) * SP_NOP, WAIT_W = SP_NV + (SP_NS - 2) * SP_NOP;
+    u32x4 xr[SP_NS][SP_NV];
+    // (the start-up issues in the loop's order, W(0) then X(1): the compiler's own count for a use of xr is the smallest over all
+    // paths to it, and a start-up with fewer operations behind X(1) would shorten the loop's wait for X for good)
+    load_x(0, xr[0]);
+#pragma unroll
+    for (int j = 0; j < SP_NS - 1; ++j) {
+        __builtin_amdgcn_sched_barrier(0);
+        request_w(j, j);
+        __builtin_amdgcn_sched_barrier(0);
+        load_x(j + 1, xr[j + 1]);
     }
-    __syncthreads();                                  // (vmcnt(0) rides in the barrier's fence: the LDS-DMA writes of every wave have landed)
-    for (int s = 0; s < nstep; ++s) {
-        const int st = s & 1;
-        const bool more = s + 1 < nstep;
-        u32x4 xv[2];
-        if (more) {
-            request_w(s + 1, st ^ 1);
-            load_x(s + 1, xv);
+    __builtin_amdgcn_sched_barrier(0);
+    write_x(0, xr[0]);
+    __builtin_amdgcn_sched_barrier(0);
+    ring_wait<SP_NV>();                               // (the wave's pieces of W(0) have landed -- only the loads of X(1) are younger -- and its
+    __builtin_amdgcn_s_barrier();                     // writes of X(0) are done: slot 0 is published)
+    __builtin_amdgcn_sched_barrier(0);
+    // (straight-line iterations, no branch inside: past the end of K the loads deliver zeros, which are written into a free ring slot)
+    auto iteration = [&](int h, auto uc) {
+        constexpr int u = decltype(uc)::value;
+        u32x4 a[2][3][4], b[2][3];
+        frags(u, 0, a[0], b[0], 0, 5);                // (in term order: the first MFMA waits for five reads, not fifteen)
+        __builtin_amdgcn_sched_barrier(0);
+        frags(u, 0, a[0], b[0], 5, 10);
+        __builtin_amdgcn_sched_barrier(0);
+        frags(u, 0, a[0], b[0], 10, 15);
+        // the first sub-step's six terms; behind each, under its four MFMAs: one piece of W(h + SP_NS - 1) -- a piece costs the wave
+        // ~100 issue cycles, which both waves of a SIMD would otherwise spend side by side behind the barrier with the MFMA unit idle
+        // -- and a share of the second sub-step's fragment reads (one exposed LDS latency per iteration instead of two)
+#pragma unroll
+        for (int tm = 0; tm < 6; ++tm) {
+            __builtin_amdgcn_sched_barrier(0);
+            mma(a[0], b[0], tm, tm + 1);
+            __builtin_amdgcn_sched_barrier(0);
+            request_w(h + SP_NS - 1, (u + SP_NS - 1) % SP_NS, tm, tm + 1);
+            frags(u, 1, a[1], b[1], tm < 3 ? 3 * tm : 9 + 2 * (tm - 3), tm < 3 ? 3 * tm + 3 : 11 + 2 * (tm - 3));
+        }
+        __builtin_amdgcn_sched_barrier(0);            // (the waits count operations in this order: W pieces, then X)
+        load_x(h + SP_NS, xr[u]);
+        __builtin_amdgcn_sched_barrier(0);
+        // the second sub-step; the split of X(h + 1) rides in the vector-ALU slots between its MFMAs, a pair of floats per term
+        // (~20 instructions under four MFMAs), the three stores after the fifth term
+        lds_dma_wait<WAIT_X>();
+        unsigned o[3][4];
+#pragma unroll
+        for (int tm = 0; tm < 6; ++tm) {
+            __builtin_amdgcn_sched_barrier(0);
+            mma(a[1], b[1], tm, tm + 1);
+            if (tm < 4) {
+                split_pair(xr[(u + 1) % SP_NS], tm, o);
+#pragma unroll
+                for (int i = 0; i < 4; ++i) {
+                    __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);        // one MFMA ...
+                    __builtin_amdgcn_sched_group_barrier(0x002, 5, 0);        // ... five vector-ALU instructions
+                }
+            }
+            if (tm == 4) store_x((u + 1) % SP_NS, o);
         }
         __builtin_amdgcn_sched_barrier(0);
-        multiply(st, 0);
+        ring_wait<WAIT_W>();
+        __builtin_amdgcn_s_barrier();
         __builtin_amdgcn_sched_barrier(0);
-        if (more) write_x(st ^ 1, xv);                // the split rides on the vector ALU under the other wave's MFMAs
-        __builtin_amdgcn_sched_barrier(0);
-        multiply(st, 1);
-        __builtin_amdgcn_sched_barrier(0);
-        lds_dma_wait<0>();                            // (this wave's LDS-DMA pieces of step s + 1 have landed; the barrier tells the others)
-        __syncthreads();
+    };
+    int h0 = 0;
+    for (; h0 + SP_NS <= nslot; h0 += SP_NS) {
+        iteration(h0, std::integral_constant<int, 0>());
+        iteration(h0 + 1, std::integral_constant<int, 1>());
     }
+    if (h0 < nslot) iteration(h0, std::integral_constant<int, 0>());          // K % 64 == 32: half a turn is left (workgroup-uniform)
+    lds_dma_wait<0>();                               // (the requests past the end of K: nothing of this wave's may land in LDS after it ends)
     if constexpr (VAR & 4) {
         if (p.act != 77) return;
     }
