@@ -106,6 +106,12 @@ SIGNATURES = {
     "ffb6d_mean_shift_workspace_bytes": (_sz, [_i32, _i64]),
     "ffb6d_mean_shift_f32": (_i32, [_vp, _vp, _i32, _i32, _i64, _i64, _c.c_float, _i32, _i32, _vp, _vp, _vp, _vp, _vp,
                                     _sz, _vp]),
+    "ffb6d_mean_shift_multi_workspace_bytes": (_sz, [_i32, _i64]),
+    "ffb6d_mean_shift_multi_f32": (_i32, [_vp, _vp, _i32, _i32, _i64, _i64, _c.c_float, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp,
+                                          _vp, _vp, _sz, _vp]),
+    "ffb6d_pose_set_converged_out": (None, [_vp]),
+    "ffb6d_set_clusters_to_points": (_i32, [_vp, _vp, _vp, _vp, _i32, _i64, _i32, _vp, _vp]),
+    "ffb6d_vote_sets_inst_f32": (_i32, [_vp, _vp, _vp, _i32, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i64, _vp, _vp, _vp]),
     "ffb6d_set_labels_to_points": (_i32, [_vp, _vp, _vp, _vp, _i32, _i64, _i32, _vp, _vp]),
     "ffb6d_refine_mask_by_center": (_i32, [_vp, _vp, _vp, _i32, _vp, _vp, _vp, _vp, _i32, _i32, _vp, _vp]),
     "ffb6d_best_fit_transform_f32": (_i32, [_vp, _vp, _i32, _i32, _vp, _vp]),

@@ -258,13 +258,16 @@ constexpr int kCap = 4096;                    // largest set the one-workgroup f
 constexpr int kCapLight = 2048;
 constexpr int fit_lds_bytes(int cap) { return (3 * 2 + 2) * cap * (int)sizeof(float) + 3 * cap * (int)sizeof(unsigned short) + 512; }
 
-template <int kBT, int kCap>
+// kMulti (ffb6d_mean_shift_multi_f32): the same rounds, then the tail peels one ball after another off the converged list instead of
+// keeping the largest only -- centers [G,K,3], n_inside [G,K], labels = cluster id u8 [G,stride], n_clusters [G]
+template <int kBT, int kCap, bool kMulti = false>
 __global__ __launch_bounds__(kBT) void mean_shift_fit_kernel(
     const float4* __restrict__ sets, const int* __restrict__ counts, int sets_per_count, int64_t stride, float k2, float thresh,
     float bandwidth, int max_iter, float* __restrict__ centers, unsigned char* __restrict__ labels, int* __restrict__ n_inside,
     int* __restrict__ iters, int* __restrict__ rounds_ws, int* __restrict__ n_large, int m_lo, int count_large,
     const float4* __restrict__ pre0, const float4* __restrict__ pre1, const unsigned* __restrict__ pre_move, int G,
-    const float4* __restrict__ sets_odd, const int* __restrict__ start_of) {
+    const float4* __restrict__ sets_odd, const int* __restrict__ start_of, int max_clusters, int min_inside, int* __restrict__ n_clusters,
+    float4* __restrict__ conv_out) {
 #pragma clang fp contract(fast)
     static_assert(kCap == 4 * kBT, "the compaction gives every thread four consecutive slots");
     // start_of != nullptr: the launch CONTINUES fits begun chip-wide (big_round_kernel / big_compact_kernel below): set g = the distinct
@@ -293,9 +296,18 @@ __global__ __launch_bounds__(kBT) void mean_shift_fit_kernel(
     if (M <= m_lo && m_lo > 0) return;                          // fitted by the smaller form (empty sets included)
     if (M <= 0 && resumed) return;
     if (M <= 0) {
-        if (tid == 0) {
+        if constexpr (kMulti) {
+            for (int s = tid; s < max_clusters; s += kBT) {
+                float* c = centers + (static_cast<int64_t>(g) * max_clusters + s) * 3;
+                c[0] = c[1] = c[2] = 0.f;
+                n_inside[static_cast<int64_t>(g) * max_clusters + s] = 0;
+            }
+            if (tid == 0) n_clusters[g] = 0;
+        } else if (tid == 0) {
             centers[3 * g] = centers[3 * g + 1] = centers[3 * g + 2] = 0.f;
             if (n_inside) n_inside[g] = 0;
+        }
+        if (tid == 0) {
             if (iters) iters[g] = 0;
             rounds_ws[g] = 0;
         }
@@ -424,6 +436,13 @@ __global__ __launch_bounds__(kBT) void mean_shift_fit_kernel(
     // ball sizes (multiplicity-weighted), winner = largest ball, ties to the lowest index = lowest original index (:50-53)
     const float *cx_ = px + cur * kCap, *cy_ = py + cur * kCap, *cz_ = pz + cur * kCap;
     const int n = (U + 7) & ~7;
+    // kMulti: the ball size of every list entry is kept (the arrays of the rounds are dead: pmn -> sizes, rep -> cluster id of
+    // the entry, nidx -> the entries a peel removed)
+    int* ball = reinterpret_cast<int*>(pmn);
+    unsigned short *cl = rep, *gone = nidx;
+    int* n_gone = reinterpret_cast<int*>(red64 + 16);
+    if constexpr (kMulti)
+        for (int q = tid; q < U; q += kBT) cl[q] = 0;
     unsigned long long key = 0ull;
     for (int i0 = 0; i0 < U; i0 += kBT / 4) {
         const int q = i0 + (tid >> 2);
@@ -439,6 +458,8 @@ __global__ __launch_bounds__(kBT) void mean_shift_fit_kernel(
         if (q < U) {
             const unsigned long long mine = (static_cast<unsigned long long>((unsigned)inside) << 32) | (0xffffffffu - static_cast<unsigned>(q));
             key = mine > key ? mine : key;
+            if constexpr (kMulti)
+                if (sub == 0) ball[q] = static_cast<int>(inside);
         }
     }
 #pragma unroll
@@ -449,6 +470,79 @@ __global__ __launch_bounds__(kBT) void mean_shift_fit_kernel(
     if (lane == 0) red64[wave] = key;
     __syncthreads();
     for (int i = 0; i < kBT / 64; ++i) key = red64[i] > key ? red64[i] : key;
+    if constexpr (kMulti) {
+        // The peel (include/ffb6d_pose.h): `key` is the winner among the entries still alive (cl == 0).  Its ball leaves, the sizes
+        // of the survivors lose the multiplicities of the removed entries within the bandwidth (the pairs of the count pass are
+        // not made again), the next winner is the arg-max of what is left.  Every thread holds the same key: uniform control flow.
+        const int64_t slot0 = static_cast<int64_t>(g) * max_clusters;
+        int k = 0;
+        while (key != 0ull && static_cast<int>(key >> 32) >= min_inside && k < max_clusters) {
+            const int w = static_cast<int>(0xffffffffu - static_cast<unsigned>(key & 0xffffffffull));
+            const float wx = cx_[w], wy = cy_[w], wz = cz_[w];
+            if (tid == 0) {
+                float* c = centers + (slot0 + k) * 3;
+                c[0] = wx; c[1] = wy; c[2] = wz;
+                n_inside[slot0 + k] = static_cast<int>(key >> 32);
+                *n_gone = 0;
+            }
+            ++k;
+            __syncthreads();
+            for (int q = tid; q < U; q += kBT) {
+                if (cl[q]) continue;
+                const float dx = wx - cx_[q], dy = wy - cy_[q], dz = wz - cz_[q];
+                if (sqrtf(dx * dx + dy * dy + dz * dz) < bandwidth) {
+                    cl[q] = static_cast<unsigned short>(k);
+                    gone[atomicAdd(n_gone, 1)] = static_cast<unsigned short>(q);
+                }
+            }
+            __syncthreads();
+            const int R = *n_gone;
+            key = 0ull;
+            for (int q = tid; q < U; q += kBT) {
+                if (cl[q]) continue;
+                const float ccx = cx_[q], ccy = cy_[q], ccz = cz_[q];
+                float less = 0.f;
+                for (int r = 0; r < R; ++r) {
+                    const int x = gone[r];
+                    const float dx = ccx - cx_[x], dy = ccy - cy_[x], dz = ccz - cz_[x];
+                    less += sqrtf(dx * dx + dy * dy + dz * dz) < bandwidth ? pm[x] : 0.f;
+                }
+                const int left = ball[q] - static_cast<int>(less);
+                ball[q] = left;
+                const unsigned long long mine = (static_cast<unsigned long long>((unsigned)left) << 32) | (0xffffffffu - static_cast<unsigned>(q));
+                key = mine > key ? mine : key;
+            }
+#pragma unroll
+            for (int o = 32; o > 0; o >>= 1) {
+                const unsigned long long other = __shfl_xor(key, o);
+                key = other > key ? other : key;
+            }
+            if (lane == 0) red64[wave] = key;
+            __syncthreads();
+            for (int i = 0; i < kBT / 64; ++i) key = red64[i] > key ? red64[i] : key;
+        }
+        for (int s = k + tid; s < max_clusters; s += kBT) {
+            float* c = centers + (slot0 + s) * 3;
+            c[0] = c[1] = c[2] = 0.f;
+            n_inside[slot0 + s] = 0;
+        }
+        if (tid == 0) {
+            n_clusters[g] = k;
+            if (iters) iters[g] = made;
+            rounds_ws[g] = made;
+        }
+        for (int64_t j = tid; j < stride; j += kBT) labels[g * stride + j] = j < M ? static_cast<unsigned char>(cl[owner[j]]) : (unsigned char)0;
+        if (conv_out) {
+            // test hook (ffb6d_pose_set_converged_out): the converged position of every point; of a continued fit: of every list
+            // entry, into the list buffer this fit did not start from (big_converged_kernel carries them to the points)
+            float4* out = resumed ? const_cast<float4*>((t_first & 1) ? sets : sets_odd) : conv_out;
+            for (int j = tid; j < M; j += kBT) {
+                const int u = owner[j];
+                out[g * stride + j] = make_float4(cx_[u], cy_[u], cz_[u], resumed ? 0.f : src[j].w);
+            }
+        }
+        return;
+    }
     const int win = static_cast<int>(0xffffffffu - static_cast<unsigned>(key & 0xffffffffull));
     const float wx = cx_[win], wy = cy_[win], wz = cz_[win];
     if (tid == 0) {
@@ -554,6 +648,116 @@ __global__ __launch_bounds__(kBlock) void ball_labels_kernel(
         }
         labels[g * stride + j] = lab;
     }
+}
+
+// The peel of ffb6d_mean_shift_multi_f32 for the sets the round-by-round kernels converged (what ball_count_kernel and
+// ball_labels_kernel are for the single fit): one workgroup per set on the converged points themselves.  One pass of count^2 pairs
+// for the ball sizes (1024-point tiles in LDS, integer counts, the pair expression of ball_count_kernel), then per peel: arg-max
+// over the points still alive, the winner's ball gets the cluster id and is listed, the survivors lose one count per listed point
+// within the bandwidth.  ball [G,stride] and gone [G,stride] live in the workspace (the maps of the chip-wide rounds, dead by now);
+// the cluster id of a point doubles as its alive flag.
+constexpr int kPeelBT = 1024;
+
+__global__ __launch_bounds__(kPeelBT) void peel_points_kernel(
+    const float4* __restrict__ buf0, const float4* __restrict__ buf1, const int* __restrict__ counts, int sets_per_count, int64_t stride,
+    float bandwidth, const int* __restrict__ rounds, int max_clusters, int min_inside, float* __restrict__ centers,
+    int* __restrict__ n_inside, int* __restrict__ n_clusters, unsigned char* __restrict__ cluster, int* __restrict__ iters, int min_cnt,
+    const int* __restrict__ handed, int* __restrict__ ball_ws, unsigned* __restrict__ gone_ws, float4* __restrict__ conv_out) {
+    __shared__ float4 tile[kPeelBT];
+    __shared__ unsigned long long red64[kPeelBT / 64];
+    __shared__ int n_gone;
+    const int g = blockIdx.x;
+    const int cnt = counts[g / sets_per_count];
+    if (cnt <= min_cnt || (handed && handed[g] <= min_cnt)) return;     // results written by mean_shift_fit_kernel
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int64_t slot0 = static_cast<int64_t>(g) * max_clusters;
+    unsigned char* cl = cluster + g * stride;
+    if (tid == 0 && iters) iters[g] = rounds[g];
+    for (int64_t j = max(cnt, 0) + tid; j < stride; j += kPeelBT) cl[j] = 0;
+    int k = 0;
+    if (cnt > 0) {
+        const float4* src = ((rounds[g] & 1) ? buf1 : buf0) + g * stride;
+        int* ball = ball_ws + g * stride;
+        unsigned* gone = gone_ws + g * stride;
+        if (conv_out)                                           // test hook (ffb6d_pose_set_converged_out)
+            for (int i = tid; i < cnt; i += kPeelBT) conv_out[g * stride + i] = src[i];
+        unsigned long long key = 0ull;
+        for (int i0 = 0; i0 < cnt; i0 += kPeelBT) {
+            const int i = i0 + tid;
+            const float4 c = src[min(i, cnt - 1)];
+            int inside = 0;
+            for (int j0 = 0; j0 < cnt; j0 += kPeelBT) {
+                __syncthreads();
+                if (j0 + tid < cnt) tile[tid] = src[j0 + tid];
+                __syncthreads();
+                const int n = min(kPeelBT, cnt - j0);
+                for (int x = 0; x < n; ++x) {
+                    const float4 p = tile[x];
+                    const float dx = c.x - p.x, dy = c.y - p.y, dz = c.z - p.z;
+                    inside += sqrtf(dx * dx + dy * dy + dz * dz) < bandwidth;
+                }
+            }
+            if (i < cnt) {
+                ball[i] = inside;
+                cl[i] = 0;
+                const unsigned long long mine = (static_cast<unsigned long long>(inside) << 32) | (0xffffffffu - static_cast<unsigned>(i));
+                key = mine > key ? mine : key;
+            }
+        }
+        while (true) {
+#pragma unroll
+            for (int o = 32; o > 0; o >>= 1) {
+                const unsigned long long other = __shfl_xor(key, o);
+                key = other > key ? other : key;
+            }
+            __syncthreads();                                    // (everyone has read red64 of the previous peel)
+            if (lane == 0) red64[wave] = key;
+            __syncthreads();
+            for (int i = 0; i < kPeelBT / 64; ++i) key = red64[i] > key ? red64[i] : key;
+            if (key == 0ull || static_cast<int>(key >> 32) < min_inside || k == max_clusters) break;
+            const int w = static_cast<int>(0xffffffffu - static_cast<unsigned>(key & 0xffffffffull));
+            const float4 c = src[w];
+            if (tid == 0) {
+                float* o = centers + (slot0 + k) * 3;
+                o[0] = c.x; o[1] = c.y; o[2] = c.z;
+                n_inside[slot0 + k] = static_cast<int>(key >> 32);
+                n_gone = 0;
+            }
+            ++k;
+            __syncthreads();
+            for (int i = tid; i < cnt; i += kPeelBT) {
+                if (cl[i]) continue;
+                const float4 p = src[i];
+                const float dx = c.x - p.x, dy = c.y - p.y, dz = c.z - p.z;
+                if (sqrtf(dx * dx + dy * dy + dz * dz) < bandwidth) {
+                    cl[i] = static_cast<unsigned char>(k);
+                    gone[atomicAdd(&n_gone, 1)] = static_cast<unsigned>(i);
+                }
+            }
+            __syncthreads();
+            const int R = n_gone;
+            key = 0ull;
+            for (int i = tid; i < cnt; i += kPeelBT) {
+                if (cl[i]) continue;
+                const float4 a = src[i];
+                int left = ball[i];
+                for (int r = 0; r < R; ++r) {
+                    const float4 p = src[gone[r]];
+                    const float dx = a.x - p.x, dy = a.y - p.y, dz = a.z - p.z;
+                    left -= sqrtf(dx * dx + dy * dy + dz * dz) < bandwidth;
+                }
+                ball[i] = left;
+                const unsigned long long mine = (static_cast<unsigned long long>((unsigned)left) << 32) | (0xffffffffu - static_cast<unsigned>(i));
+                key = mine > key ? mine : key;
+            }
+        }
+    }
+    for (int s = k + tid; s < max_clusters; s += kPeelBT) {
+        float* o = centers + (slot0 + s) * 3;
+        o[0] = o[1] = o[2] = 0.f;
+        n_inside[slot0 + s] = 0;
+    }
+    if (tid == 0) n_clusters[g] = k;
 }
 
 // ---- sets of more than kCap points: chip-wide rounds WITH duplicate merging, then the one-workgroup fit (round 6) -------------
@@ -720,21 +924,37 @@ __global__ __launch_bounds__(kBlock) void big_labels_kernel(
     labels[g * stride + j] = j < counts[g / sets_per_count] ? fit_labels[g * stride + owner[g * stride + j]] : (unsigned char)0;
 }
 
+// test hook (ffb6d_pose_set_converged_out): converged positions of the list entries -> of the original points
+__global__ __launch_bounds__(kBlock) void big_converged_kernel(
+    const int* __restrict__ big_ids, const int* __restrict__ counts, int sets_per_count, int64_t stride, const int* __restrict__ len_of,
+    int cap, const int* __restrict__ state_of, const float4* __restrict__ buf0, const float4* __restrict__ buf1,
+    const unsigned* __restrict__ owner, const float4* __restrict__ sets, float4* __restrict__ conv_out) {
+    const int g = big_ids[blockIdx.y];
+    if (len_of[g] > cap) return;                                // (left to the round-by-round path)
+    const int64_t j = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+    if (j >= counts[g / sets_per_count]) return;
+    const float4 c = (((state_of[g] & 0xffff) & 1) ? buf0 : buf1)[g * stride + owner[g * stride + j]];
+    conv_out[g * stride + j] = make_float4(c.x, c.y, c.z, sets[g * stride + j].w);
+}
+
 template <typename MaskT>
 __global__ __launch_bounds__(kBlock) void vote_sets_kernel(
     const float* __restrict__ pcld, const float* __restrict__ offsets, const MaskT* __restrict__ mask,
     const unsigned char* __restrict__ keep, const int* __restrict__ frame_of, const int* __restrict__ class_of,
-    int S, int N, int64_t stride, float4* __restrict__ sets, int* __restrict__ counts) {
+    int S, int N, int64_t stride, float4* __restrict__ sets, int* __restrict__ counts,
+    const unsigned char* __restrict__ inst, const int* __restrict__ inst_of) {
     __shared__ int wave_total[kBlock / 64];
     const int p = blockIdx.x;
     const int b = frame_of[p];
     const MaskT cls = static_cast<MaskT>(class_of[p]);
+    const int want = inst ? inst_of[p] : 0;                    // ffb6d_vote_sets_inst_f32: the points of one instance of the class
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     int base = 0;
     for (int i0 = 0; i0 < N; i0 += kBlock) {
         const int i = i0 + threadIdx.x;
         bool sel = false;
-        if (i < N) sel = mask[static_cast<int64_t>(b) * N + i] == cls && (!keep || keep[static_cast<int64_t>(b) * N + i]);
+        if (i < N) sel = mask[static_cast<int64_t>(b) * N + i] == cls && (!keep || keep[static_cast<int64_t>(b) * N + i]) &&
+                         (!inst || inst[static_cast<int64_t>(b) * N + i] == want);
         const unsigned long long bal = __ballot(sel);
         const int before = __popcll(bal & ((1ull << lane) - 1ull));
         __syncthreads();
@@ -845,9 +1065,10 @@ static int g_big_form = 1;
 void ffb6d_pose_set_big_form(int form) { g_big_form = form; }
 
 
-int ffb6d_vote_sets_f32(const float* pcld, const float* offsets, const void* mask, int mask_bits,
-                        const unsigned char* keep, const int* frame_of, const int* class_of, int n_pairs, int B,
-                        int S, int N, int64_t set_stride, float* sets, int* counts, ffb6d_stream_t stream) {
+static int vote_sets_run(const float* pcld, const float* offsets, const void* mask, int mask_bits,
+                         const unsigned char* keep, const int* frame_of, const int* class_of, int n_pairs, int B,
+                         int S, int N, int64_t set_stride, float* sets, int* counts, ffb6d_stream_t stream,
+                         const unsigned char* inst, const int* inst_of) {
     FFB6D_REQUIRE(n_pairs >= 0 && B > 0 && S > 0 && N > 0, "vote_sets: bad sizes n_pairs=%d B=%d S=%d N=%d", n_pairs, B, S, N);
     FFB6D_REQUIRE(mask_bits == 32 || mask_bits == 64, "vote_sets: mask_bits must be 32 or 64, got %d", mask_bits);
     FFB6D_REQUIRE(set_stride >= N, "vote_sets: set_stride %lld < N %d", (long long)set_stride, N);
@@ -857,13 +1078,29 @@ int ffb6d_vote_sets_f32(const float* pcld, const float* offsets, const void* mas
     if (mask_bits == 64)
         vote_sets_kernel<int64_t><<<n_pairs, kBlock, 0, st>>>(pcld, offsets, static_cast<const int64_t*>(mask), keep,
                                                                frame_of, class_of, S, N, set_stride,
-                                                               reinterpret_cast<float4*>(sets), counts);
+                                                               reinterpret_cast<float4*>(sets), counts, inst, inst_of);
     else
         vote_sets_kernel<int32_t><<<n_pairs, kBlock, 0, st>>>(pcld, offsets, static_cast<const int32_t*>(mask), keep,
                                                                frame_of, class_of, S, N, set_stride,
-                                                               reinterpret_cast<float4*>(sets), counts);
+                                                               reinterpret_cast<float4*>(sets), counts, inst, inst_of);
     FFB6D_LAUNCH_CHECK();
     return 0;
+}
+
+int ffb6d_vote_sets_f32(const float* pcld, const float* offsets, const void* mask, int mask_bits,
+                        const unsigned char* keep, const int* frame_of, const int* class_of, int n_pairs, int B,
+                        int S, int N, int64_t set_stride, float* sets, int* counts, ffb6d_stream_t stream) {
+    return vote_sets_run(pcld, offsets, mask, mask_bits, keep, frame_of, class_of, n_pairs, B, S, N, set_stride, sets, counts, stream,
+                         nullptr, nullptr);
+}
+
+int ffb6d_vote_sets_inst_f32(const float* pcld, const float* offsets, const void* mask, int mask_bits,
+                             const unsigned char* inst, const int* frame_of, const int* class_of, const int* inst_of,
+                             int n_pairs, int B, int S, int N, int64_t set_stride, float* sets, int* counts,
+                             ffb6d_stream_t stream) {
+    FFB6D_REQUIRE(n_pairs == 0 || (inst && inst_of), "vote_sets_inst: null pointer");
+    return vote_sets_run(pcld, offsets, mask, mask_bits, nullptr, frame_of, class_of, n_pairs, B, S, N, set_stride, sets, counts, stream,
+                         inst, inst_of);
 }
 
 size_t ffb6d_mean_shift_workspace_bytes(int G, int64_t set_stride) {
@@ -875,10 +1112,41 @@ size_t ffb6d_mean_shift_workspace_bytes(int G, int64_t set_stride) {
            2 * align256(static_cast<size_t>(G) * set_stride * sizeof(unsigned)) + align256(5 * sizeof(int) * G);
 }
 
-int ffb6d_mean_shift_f32(const float* sets, const int* counts, int sets_per_count, int G, int64_t set_stride,
-                         int64_t max_count, float bandwidth, int max_iter, int check_every, float* centers,
-                         unsigned char* labels,
-                         int* n_inside, int* iters, void* workspace, size_t workspace_bytes, ffb6d_stream_t stream) {
+}  // extern "C"
+
+// test hook (ffb6d_pose_set_converged_out)
+static float4* g_converged_out = nullptr;
+
+namespace {
+
+// ffb6d_mean_shift_multi_f32: K > 0 selects the peeling tails; centers [G,K,3], labels = cluster u8 [G,stride], n_inside [G,K]
+struct MultiArgs {
+    int K = 0, min_inside = 1;
+    int* n_clusters = nullptr;
+    float4* conv = nullptr;                                     // test hook: converged position of every point, [G,stride]
+};
+
+// the four instantiations of the one-workgroup fit behind one launch
+struct FitLaunch {
+    hipStream_t st;
+    unsigned G;
+    MultiArgs multi;
+    template <typename... A>
+    void operator()(bool light, A... a) const {
+        if (multi.K > 0) {
+            if (light) mean_shift_fit_kernel<512, kCapLight, true><<<G, 512, fit_lds_bytes(kCapLight), st>>>(a..., multi.K, multi.min_inside, multi.n_clusters, multi.conv);
+            else mean_shift_fit_kernel<1024, kCap, true><<<G, 1024, fit_lds_bytes(kCap), st>>>(a..., multi.K, multi.min_inside, multi.n_clusters, multi.conv);
+        } else {
+            if (light) mean_shift_fit_kernel<512, kCapLight><<<G, 512, fit_lds_bytes(kCapLight), st>>>(a..., 0, 0, static_cast<int*>(nullptr), static_cast<float4*>(nullptr));
+            else mean_shift_fit_kernel<1024, kCap><<<G, 1024, fit_lds_bytes(kCap), st>>>(a..., 0, 0, static_cast<int*>(nullptr), static_cast<float4*>(nullptr));
+        }
+    }
+};
+
+int mean_shift_run(const float* sets, const int* counts, int sets_per_count, int G, int64_t set_stride,
+                   int64_t max_count, float bandwidth, int max_iter, int check_every, float* centers,
+                   unsigned char* labels,
+                   int* n_inside, int* iters, void* workspace, size_t workspace_bytes, ffb6d_stream_t stream, const MultiArgs multi) {
     FFB6D_REQUIRE(G >= 0 && set_stride > 0 && sets_per_count > 0, "mean_shift: bad sizes G=%d stride=%lld", G,
                   (long long)set_stride);
     FFB6D_REQUIRE(bandwidth > 0.f && max_iter >= 0 && check_every >= 0, "mean_shift: bad bandwidth/max_iter");
@@ -925,6 +1193,10 @@ int ffb6d_mean_shift_f32(const float* sets, const int* counts, int sets_per_coun
                                          hipFuncAttributeMaxDynamicSharedMemorySize, fit_lds_bytes(kCap)) == hipSuccess &&
                      hipFuncSetAttribute(reinterpret_cast<const void*>(&mean_shift_fit_kernel<512, kCapLight>),
                                          hipFuncAttributeMaxDynamicSharedMemorySize, fit_lds_bytes(kCapLight)) == hipSuccess &&
+                     hipFuncSetAttribute(reinterpret_cast<const void*>(&mean_shift_fit_kernel<1024, kCap, true>),
+                                         hipFuncAttributeMaxDynamicSharedMemorySize, fit_lds_bytes(kCap)) == hipSuccess &&
+                     hipFuncSetAttribute(reinterpret_cast<const void*>(&mean_shift_fit_kernel<512, kCapLight, true>),
+                                         hipFuncAttributeMaxDynamicSharedMemorySize, fit_lds_bytes(kCapLight)) == hipSuccess &&
                      hipFuncSetAttribute(reinterpret_cast<const void*>(&mean_shift_spread_round_kernel),
                                          hipFuncAttributeMaxDynamicSharedMemorySize, 4 * sizeof(float) * kCap) == hipSuccess;
             if (fit_ok) ffb6d::cache_set(attr_set, slot, 1);
@@ -932,6 +1204,7 @@ int ffb6d_mean_shift_f32(const float* sets, const int* counts, int sets_per_coun
         }
     }
     const int min_cnt = fit_ok ? kCap : -1;                    // sets above it are fitted round by round
+    const FitLaunch fit{st, static_cast<unsigned>(G), multi};
     if (fit_ok) {
         const float4* s4 = reinterpret_cast<const float4*>(sets);
         // the first two rounds of the sets of kSpreadMin .. kCap points, 128 points per workgroup
@@ -961,19 +1234,16 @@ int ffb6d_mean_shift_f32(const float* sets, const int* counts, int sets_per_coun
             pre1 = buf1;
         }
         if (g_fit_form == 1) {
-            mean_shift_fit_kernel<512, kCapLight><<<static_cast<unsigned>(G), 512, fit_lds_bytes(kCapLight), st>>>(
-                s4, counts, sets_per_count, set_stride, k2, thresh, bandwidth, max_iter, centers, labels, n_inside, iters, rounds, n_large, 0, 0,
+            fit(true, s4, counts, sets_per_count, set_stride, k2, thresh, bandwidth, max_iter, centers, labels, n_inside, iters, rounds, n_large, 0, 0,
                 pre0, pre1, shift, G, nullptr, nullptr);
             FFB6D_LAUNCH_CHECK();
             if (set_stride > kCapLight) {
-                mean_shift_fit_kernel<1024, kCap><<<static_cast<unsigned>(G), 1024, fit_lds_bytes(kCap), st>>>(
-                    s4, counts, sets_per_count, set_stride, k2, thresh, bandwidth, max_iter, centers, labels, n_inside, iters, rounds, n_large,
+                fit(false, s4, counts, sets_per_count, set_stride, k2, thresh, bandwidth, max_iter, centers, labels, n_inside, iters, rounds, n_large,
                     kCapLight, 1, pre0, pre1, shift, G, nullptr, nullptr);
                 FFB6D_LAUNCH_CHECK();
             }
         } else {
-            mean_shift_fit_kernel<1024, kCap><<<static_cast<unsigned>(G), 1024, fit_lds_bytes(kCap), st>>>(
-                s4, counts, sets_per_count, set_stride, k2, thresh, bandwidth, max_iter, centers, labels, n_inside, iters, rounds, n_large, 0, 1,
+            fit(false, s4, counts, sets_per_count, set_stride, k2, thresh, bandwidth, max_iter, centers, labels, n_inside, iters, rounds, n_large, 0, 1,
                 pre0, pre1, shift, G, nullptr, nullptr);
             FFB6D_LAUNCH_CHECK();
         }
@@ -1038,18 +1308,22 @@ int ffb6d_mean_shift_f32(const float* sets, const int* counts, int sets_per_coun
         // the fits continue from the lists (sets whose list is still longer: untouched, counted below)
         unsigned char* fit_labels = labels ? reinterpret_cast<unsigned char*>(rep) : nullptr;       // (the representatives are dead)
         if (g_fit_form == 1) {
-            mean_shift_fit_kernel<512, kCapLight><<<static_cast<unsigned>(G), 512, fit_lds_bytes(kCapLight), st>>>(
-                buf0, len_of, 1, set_stride, k2, thresh, bandwidth, max_iter, centers, fit_labels, n_inside, iters, rounds, n_large, 0, 0,
+            fit(true, buf0, len_of, 1, set_stride, k2, thresh, bandwidth, max_iter, centers, fit_labels, n_inside, iters, rounds, n_large, 0, 0,
                 nullptr, nullptr, nullptr, G, buf1, state_of);
             FFB6D_LAUNCH_CHECK();
         }
-        mean_shift_fit_kernel<1024, kCap><<<static_cast<unsigned>(G), 1024, fit_lds_bytes(kCap), st>>>(
-            buf0, len_of, 1, set_stride, k2, thresh, bandwidth, max_iter, centers, fit_labels, n_inside, iters, rounds, n_large,
+        fit(false, buf0, len_of, 1, set_stride, k2, thresh, bandwidth, max_iter, centers, fit_labels, n_inside, iters, rounds, n_large,
             g_fit_form == 1 ? kCapLight : 0, 0, nullptr, nullptr, nullptr, G, buf1, state_of);
         FFB6D_LAUNCH_CHECK();
         if (labels) {
             big_labels_kernel<<<dim3(static_cast<unsigned>(ceil_div(set_stride, kBlock)), n_big), kBlock, 0, st>>>(
                 big_ids, counts, sets_per_count, set_stride, len_of, kCap, fit_labels, owner, labels);
+            FFB6D_LAUNCH_CHECK();
+        }
+        if (multi.conv) {
+            big_converged_kernel<<<dim3(static_cast<unsigned>(ceil_div(set_stride, kBlock)), n_big), kBlock, 0, st>>>(
+                big_ids, counts, sets_per_count, set_stride, len_of, kCap, state_of, buf0, buf1, owner, reinterpret_cast<const float4*>(sets),
+                multi.conv);
             FFB6D_LAUNCH_CHECK();
         }
         bool left = false;
@@ -1089,6 +1363,13 @@ int ffb6d_mean_shift_f32(const float* sets, const int* counts, int sets_per_coun
             if (all_done) break;
         }
     }
+    if (multi.K > 0) {
+        peel_points_kernel<<<static_cast<unsigned>(G), kPeelBT, 0, st>>>(buf0, buf1, counts, sets_per_count, set_stride, bandwidth, rounds, multi.K,
+                                                                          multi.min_inside, centers, n_inside, multi.n_clusters, labels, iters, min_cnt,
+                                                                          handed, reinterpret_cast<int*>(rep), owner, multi.conv);
+        FFB6D_LAUNCH_CHECK();
+        return 0;
+    }
     ball_count_kernel<<<grid, kBlock, 0, st>>>(buf0, buf1, counts, sets_per_count, set_stride, bandwidth, rounds, best, min_cnt, handed);
     FFB6D_LAUNCH_CHECK();
     const dim3 lgrid(static_cast<unsigned>(labels ? ceil_div(set_stride, kBlock) : 1), static_cast<unsigned>(G));
@@ -1096,6 +1377,44 @@ int ffb6d_mean_shift_f32(const float* sets, const int* counts, int sets_per_coun
                                                  centers, labels, n_inside, iters, min_cnt, handed);
     FFB6D_LAUNCH_CHECK();
     return 0;
+}
+
+}  // namespace
+
+extern "C" {
+
+int ffb6d_mean_shift_f32(const float* sets, const int* counts, int sets_per_count, int G, int64_t set_stride,
+                         int64_t max_count, float bandwidth, int max_iter, int check_every, float* centers,
+                         unsigned char* labels,
+                         int* n_inside, int* iters, void* workspace, size_t workspace_bytes, ffb6d_stream_t stream) {
+    return mean_shift_run(sets, counts, sets_per_count, G, set_stride, max_count, bandwidth, max_iter, check_every, centers, labels,
+                          n_inside, iters, workspace, workspace_bytes, stream, MultiArgs{});
+}
+
+void ffb6d_pose_set_converged_out(float* out) { g_converged_out = reinterpret_cast<float4*>(out); }
+
+// the peel needs no memory of its own: sizes and removed lists live in maps of the chip-wide rounds that are dead by then
+size_t ffb6d_mean_shift_multi_workspace_bytes(int G, int64_t set_stride) { return ffb6d_mean_shift_workspace_bytes(G, set_stride); }
+
+int ffb6d_mean_shift_multi_f32(const float* sets, const int* counts, int sets_per_count, int G, int64_t set_stride,
+                               int64_t max_count, float bandwidth, int max_iter, int check_every, int max_clusters,
+                               int min_inside, float* centers, unsigned char* cluster, int* n_inside, int* n_clusters,
+                               int* iters, void* workspace, size_t workspace_bytes, ffb6d_stream_t stream) {
+    FFB6D_REQUIRE(max_clusters >= 1 && max_clusters <= 255, "mean_shift_multi: max_clusters %d outside [1, 255] (ids are u8)", max_clusters);
+    FFB6D_REQUIRE(min_inside >= 1, "mean_shift_multi: min_inside %d < 1", min_inside);
+    FFB6D_REQUIRE(G <= 0 || (cluster && n_inside && n_clusters), "mean_shift_multi: null pointer");
+    MultiArgs multi;
+    multi.K = max_clusters;
+    multi.min_inside = min_inside;
+    multi.n_clusters = n_clusters;
+    multi.conv = g_converged_out;
+    return mean_shift_run(sets, counts, sets_per_count, G, set_stride, max_count, bandwidth, max_iter, check_every, centers, cluster,
+                          n_inside, iters, workspace, workspace_bytes, stream, multi);
+}
+
+int ffb6d_set_clusters_to_points(const float* sets, const unsigned char* cluster, const int* counts, const int* frame_of,
+                                 int n_pairs, int64_t set_stride, int N, unsigned char* inst, ffb6d_stream_t stream) {
+    return ffb6d_set_labels_to_points(sets, cluster, counts, frame_of, n_pairs, set_stride, N, inst, stream);
 }
 
 int ffb6d_set_labels_to_points(const float* sets, const unsigned char* labels, const int* counts, const int* frame_of,

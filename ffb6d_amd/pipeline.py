@@ -27,14 +27,20 @@ class SensorToPose:
     pose_inputs: optional callable (inp, out) -> (pcld [B,N,3], mask [B,N], ctr_of [B,1,N,3], kp_of [B,n_kps,N,3]) replacing the
     network's own votes (benchmarks with random weights feed a synthetic 5-object vote field; the stage still waits for the forward).
     refine: None, or the dict pose.solve_poses takes (models=refine.PreparedModels, max_iter, max_dist, ...): ICP refinement of the
-    fitted poses as the last step of stage C (on the pose side stream under the overlapped schedule)."""
+    fitted poses as the last step of stage C (on the pose side stream under the overlapped schedule).
+    max_instances: None = one pose per (frame, class) through pose.solve_poses (above); an integer K = stage C is
+    pose.solve_instances: up to K scored instances per (frame, class), `solve` then returns its dict of device tensors (the rows
+    bop.BOPSceneEval.add_batch takes).  Not with `refine` (ICP selects its scene points by class)."""
 
     def __init__(self, net, K, n_points, mesh_kps, mesh_ctr, r_lst=None, classes=None, normals="depth", cam_scale=1.0,
-                 pose_inputs=None, seed=0, refine=None):
+                 pose_inputs=None, seed=0, refine=None, max_instances=None):
         self.net, self.K, self.n_points = net, np.asarray(K, np.float64), int(n_points)
         self.mesh_kps, self.mesh_ctr, self.r_lst, self.classes = mesh_kps, mesh_ctr, r_lst, classes
         self.normals, self.cam_scale, self.pose_inputs, self.seed = normals, float(cam_scale), pose_inputs, int(seed)
         self.refine = refine
+        if max_instances is not None and refine is not None:
+            raise ValueError("max_instances and refine exclude each other: ICP refinement is defined for one instance per class")
+        self.max_instances = None if max_instances is None else int(max_instances)
         self.dev = next(net.parameters()).device
         self._streams = None
 
@@ -58,12 +64,15 @@ class SensorToPose:
             return self.net({k: inp[k] for k in ("rgb", "cld_rgb_nrm", "choose", "dpt_xyz")})
 
     def solve(self, inp, out):
-        """-> list over frames of (class ids, poses [n,3,4] float64, keypoints [n,n_kps+1,3]) (pose.solve_poses)"""
+        """-> list over frames of (class ids, poses [n,3,4] float64, keypoints [n,n_kps+1,3]) (pose.solve_poses); with
+        max_instances the dict of pose.solve_instances"""
         if self.pose_inputs is not None:
             pcld, mask, ctr_of, kp_of = self.pose_inputs(inp, out)
         else:
             pcld, mask = inp["cld"], out["pred_rgbd_segs"].argmax(dim=1)            # train_lm.py:385 / demo.py:160
             ctr_of, kp_of = out["pred_ctr_ofs"], out["pred_kp_ofs"]
+        if self.max_instances is not None:
+            return _pose.solve_instances(pcld, mask, ctr_of, kp_of, self.mesh_kps, self.mesh_ctr, self.max_instances, classes=self.classes)
         return _pose.solve_poses(pcld, mask, ctr_of, kp_of, self.mesh_kps, self.mesh_ctr, r_lst=self.r_lst, classes=self.classes,
                                  refine=self.refine)
 

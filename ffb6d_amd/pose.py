@@ -1,12 +1,13 @@
 """Pose solver on the GPU: the step after FFB6D.forward.
 
 Host-side mirror of the reference's
-    MeanShiftTorch                      ffb6d/utils/meanshift_pytorch.py:27-58
+    MeanShiftTorch                      ffb6d/utils/meanshift_pytorch.py:27-85 (fit, fit_multi_clus)
     best_fit_transform                  ffb6d/utils/pvn3d_eval_utils_kpls.py:28-61
     cal_frame_poses / cal_frame_poses_lm   ffb6d/utils/pvn3d_eval_utils_kpls.py:65-158,220-285
 over the C ABI of include/ffb6d_pose.h.  The reference solves one object at a time (one mean
 shift for the centre, one per keypoint, each with host round trips); `solve_poses` runs all
-(frame, object, keypoint) vote sets of a batch through the same launches.
+(frame, object, keypoint) vote sets of a batch through the same launches; `solve_instances` does the same for
+every centre cluster of a class (several instances of an object in a frame), each with a score.
 
 The mesh keypoints / centres / radii the reference reads from dataset files through
 `Basic_Utils` (pvn3d_eval_utils_kpls.py:149-152,277-280, common.py:89-94) are arguments here.
@@ -91,6 +92,67 @@ def mean_shift(sets, counts, bandwidth, max_iter=300, sets_per_count=1, want_lab
     return centers, (labels.bool() if labels is not None else None), n_inside, rounds
 
 
+MAX_CLUSTERS = 255     # cluster ids are u8 in the C ABI (include/ffb6d_pose.h)
+
+
+def vote_sets_inst(pcld, offsets, mask, inst, frame_of, class_of, inst_of):
+    """vote_sets per instance: row p takes the points with mask == class_of[p] and inst == inst_of[p] (inst u8 [B,N], the
+    map written by `instance_map`)."""
+    _need_gpu(pcld, offsets, mask, inst)
+    B, N, _ = pcld.shape
+    S = offsets.shape[1]
+    P = frame_of.numel()
+    pcld, offsets, mask = pcld.contiguous().float(), offsets.contiguous().float(), mask.contiguous()
+    sets = torch.empty((P * S, N, 4), dtype=torch.float32, device=pcld.device)
+    counts = torch.zeros((P,), dtype=torch.int32, device=pcld.device)
+    with torch.cuda.device(pcld.device), _lib.traced("vote_sets", 4 * (3 * B * N * (S + 1)) + 16 * P * S * N, (P, S, N)):
+        rc = _lib.load().ffb6d_vote_sets_inst_f32(
+            pcld.data_ptr(), offsets.data_ptr(), mask.data_ptr(), _mask_bits(mask), inst.data_ptr(), frame_of.data_ptr(),
+            class_of.data_ptr(), inst_of.data_ptr(), P, B, S, N, N, sets.data_ptr(), counts.data_ptr(), _stream(pcld))
+    _lib.check(rc, "ffb6d_vote_sets_inst_f32")
+    return sets, counts
+
+
+def mean_shift_multi(sets, counts, bandwidth, max_clusters, min_inside=1, max_iter=300, sets_per_count=1,
+                     check_every=CHECK_EVERY, workspace=None):
+    """MeanShiftTorch.fit_multi_clus for every set (the rule is stated in include/ffb6d_pose.h): sets f32 [G,M,4], counts i32
+    [G/sets_per_count] -> centers f32 [G,K,3], cluster u8 [G,M] (0 = in no returned cluster), n_inside i32 [G,K],
+    n_clusters i32 [G], rounds i32 [G]; K = max_clusters (1 .. 255), balls smaller than min_inside end a set's sequence.
+    workspace: None, or a uint8 tensor of at least ffb6d_mean_shift_multi_workspace_bytes(G, M) bytes."""
+    _need_gpu(sets, counts)
+    G, M, _ = sets.shape
+    K = int(max_clusters)
+    dev = sets.device
+    lib = _lib.load()
+    centers = torch.empty((G, max(K, 0), 3), dtype=torch.float32, device=dev)
+    cluster = torch.empty((G, M), dtype=torch.uint8, device=dev)
+    n_inside = torch.empty((G, max(K, 0)), dtype=torch.int32, device=dev)
+    n_clusters = torch.empty((G,), dtype=torch.int32, device=dev)
+    rounds = torch.empty((G,), dtype=torch.int32, device=dev)
+    if workspace is None:
+        workspace = torch.empty((max(lib.ffb6d_mean_shift_multi_workspace_bytes(G, M), 1),), dtype=torch.uint8, device=dev)
+    _need_gpu(workspace)
+    with torch.cuda.device(dev), _lib.traced("mean_shift_multi", 16 * G * M, (G, M, K)):
+        rc = lib.ffb6d_mean_shift_multi_f32(
+            sets.data_ptr(), counts.data_ptr(), sets_per_count, G, M, 0, float(bandwidth), int(max_iter), int(check_every), K,
+            int(min_inside), centers.data_ptr(), cluster.data_ptr(), n_inside.data_ptr(), n_clusters.data_ptr(), rounds.data_ptr(),
+            workspace.data_ptr(), workspace.numel(), _stream(sets))
+    _lib.check(rc, "ffb6d_mean_shift_multi_f32")
+    return centers, cluster, n_inside, n_clusters, rounds
+
+
+def instance_map(sets, cluster, counts, frame_of, B, N):
+    """inst u8 [B,N]: 0, or the cluster id of the point's centre vote (sets / cluster / counts of the centre-vote sets of the
+    (frame, class) pairs; ffb6d_set_clusters_to_points)."""
+    _need_gpu(sets, cluster, counts, frame_of)
+    inst = torch.zeros((B, N), dtype=torch.uint8, device=sets.device)
+    with torch.cuda.device(sets.device):
+        rc = _lib.load().ffb6d_set_clusters_to_points(sets.data_ptr(), cluster.data_ptr(), counts.data_ptr(), frame_of.data_ptr(),
+                                                     frame_of.numel(), sets.shape[1], N, inst.data_ptr(), _stream(sets))
+    _lib.check(rc, "ffb6d_set_clusters_to_points")
+    return inst
+
+
 class MeanShiftTorch:
     """Same constructor and `fit` contract as the reference class (meanshift_pytorch.py:27-58):
     fit(A [N,3] on the GPU) -> (centre [3], labels bool [N])."""
@@ -117,6 +179,24 @@ class MeanShiftTorch:
             raise ValueError(f"expected a non-empty [N,3] tensor, got {tuple(A.shape)}")
         centers, labels = self.fit_batch([A])
         return centers[0], labels[0]
+
+    def fit_multi_clus(self, A, max_clusters=None):
+        """The reference's return contract (meanshift_pytorch.py:60-85): (list of centres [3], int labels [N] with ids 1..,
+        list of ball sizes).  max_clusters=None: every cluster as the reference returns them, up to the 255 ids of the C ABI
+        (a set that needs more raises); an integer K: the first K of that sequence, points of later clusters labelled 0."""
+        _need_gpu(A)
+        if A.dim() != 2 or A.shape[1] != 3 or A.shape[0] < 1:
+            raise ValueError(f"expected a non-empty [N,3] tensor, got {tuple(A.shape)}")
+        N = int(A.shape[0])
+        sets = torch.zeros((1, N, 4), dtype=torch.float32, device=A.device)
+        sets[0, :, :3] = A
+        K = MAX_CLUSTERS if max_clusters is None else int(max_clusters)
+        centers, cluster, n_inside, n_clusters, _ = mean_shift_multi(sets, _i32([N], A.device), self.bandwidth, K, 1, self.max_iter)
+        n = int(n_clusters[0])
+        labels = cluster[0].int()
+        if max_clusters is None and n == K and bool((labels == 0).any()):
+            raise ValueError(f"the set has more than {MAX_CLUSTERS} clusters (cluster ids are u8); pass max_clusters")
+        return [centers[0, k] for k in range(n)], labels, [int(v) for v in n_inside[0, :n].tolist()]
 
 
 def best_fit_transform_batch(model, found):
@@ -256,6 +336,91 @@ def solve_poses(pcld, mask, ctr_of, kp_of, mesh_kps, mesh_ctr, r_lst=None, use_c
         sel = frame_np == b
         out.append((class_np[sel].astype(np.int64), T[sel], found[sel]))
     return out
+
+
+def _frame_class_pairs(mask, classes, B, n_cls):
+    """(frame, class) pairs as solve_poses forms them: classes=None reads the classes present per frame back from the mask."""
+    if classes is None:
+        present = torch.zeros((B, n_cls), dtype=torch.bool, device=mask.device)
+        present.scatter_(1, mask.clamp(0, n_cls - 1).long(), True)
+        present[:, 0] = False
+        present = present.cpu().numpy()
+        per_frame = [np.nonzero(present[b])[0] for b in range(B)]
+    else:
+        per_frame = [np.asarray(classes, np.int64) for _ in range(B)]
+    frame_np = np.concatenate([np.full(len(c), b, np.int32) for b, c in enumerate(per_frame)]) if B else np.zeros(0, np.int32)
+    class_np = np.concatenate(per_frame).astype(np.int32) if B else np.zeros(0, np.int32)
+    return frame_np, class_np
+
+
+def solve_instances(pcld, mask, ctr_of, kp_of, mesh_kps, mesh_ctr, max_instances, min_inside=1, min_fraction=0.0, classes=None,
+                    use_ctr=True, radius=RADIUS, max_iter=300, stats=None, **unsupported):
+    """Every instance of every class of every frame, scored: the centre votes of a (frame, class) pair go through
+    `mean_shift_multi` (up to max_instances centre clusters, largest first), every cluster becomes an estimate whose keypoint
+    votes are those of the points whose centre vote lies in the cluster.  Inputs as solve_poses.
+      max_instances  1 .. 255: cap per (frame, class);  min_inside: smallest centre cluster (in votes) that is an instance;
+      min_fraction   drops instances whose score is below it.
+    Returns a dict of DEVICE tensors, rows ordered by (frame, class, instance):
+      est_RT f64 [E,3,4], est_class / est_frame / est_instance i32 [E] (instance ids 1..), est_score f32 [E],
+      kps f32 [E,n_kps+1,3] (keypoints, then the centre), n_inside i32 [E]
+    -- est_RT, est_class, est_frame, est_score are what bop.BOPSceneEval.add_batch takes.
+    est_score = n_inside / (points of the class in the frame): the share of the class's centre votes that agree on the
+    instance, in (0, 1]; the scores of a (frame, class) sum to at most 1.  Computed on the device.
+    One read-back: the table of valid (pair, cluster) slots is turned into row indices (torch.nonzero), which sizes E -- after
+    the centre pass, before the keypoint votes are gathered.  (classes=None reads the present classes back first, as solve_poses.)
+    Not done here, because both are tied to ONE instance per class: the cross-class centre mask filter (`refine_mask` of
+    solve_poses; ffb6d_refine_mask_by_center takes one centre per pair) and ICP refinement (`refine=`; refine.icp_refine selects
+    its scene points by class).  Passing either raises."""
+    if unsupported:
+        raise TypeError(f"solve_instances does not take {sorted(unsupported)}: the centre mask filter and ICP refinement are "
+                        "defined for one instance per class (use solve_poses)")
+    _need_gpu(pcld, mask, ctr_of, kp_of)
+    B, N, _ = pcld.shape
+    n_kps = kp_of.shape[1]
+    dev = pcld.device
+    K = int(max_instances)
+    on_device = lambda x: torch.is_tensor(x) and x.is_cuda                                                                  # noqa: E731
+    mesh_kps = mesh_kps.to(device=dev, dtype=torch.float32) if on_device(mesh_kps) else torch.as_tensor(np.asarray(mesh_kps, np.float32), device=dev)
+    mesh_ctr = mesh_ctr.to(device=dev, dtype=torch.float32) if on_device(mesh_ctr) else torch.as_tensor(np.asarray(mesh_ctr, np.float32), device=dev)
+    mask = mask.contiguous()
+    frame_np, class_np = _frame_class_pairs(mask, classes, B, mesh_kps.shape[0])
+    P = len(class_np)
+    i32 = lambda n: torch.zeros((n,), dtype=torch.int32, device=dev)                                                        # noqa: E731
+    empty = dict(est_RT=torch.zeros((0, 3, 4), dtype=torch.float64, device=dev), est_class=i32(0), est_frame=i32(0), est_instance=i32(0),
+                 est_score=torch.zeros((0,), dtype=torch.float32, device=dev),
+                 kps=torch.zeros((0, n_kps + 1, 3), dtype=torch.float32, device=dev), n_inside=i32(0))
+    if P == 0:
+        return empty
+    frame_of, class_of = _i32(frame_np, dev), _i32(class_np, dev)
+    ctr_of = ctr_of.contiguous().float()
+    pcld = pcld.contiguous().float()
+
+    # 1. centre clusters of every (frame, class)
+    sets, counts = vote_sets(pcld, ctr_of, mask, frame_of, class_of)
+    centers, cluster, n_in, n_clus, rounds = mean_shift_multi(sets, counts, radius, K, min_inside, max_iter)
+    if stats is not None:
+        stats["rounds_ctr"], stats["counts_ctr"], stats["n_clusters"] = rounds, counts, n_clus
+    # 2. instance id of every point
+    inst = instance_map(sets, cluster, counts, frame_of, B, N)
+    # 3. one row per found instance (the sizes do not increase along k: the kept slots of a pair are a prefix)
+    score = n_in.float() / counts.clamp(min=1).float()[:, None]
+    valid = (torch.arange(K, device=dev)[None, :] < n_clus[:, None]) & (score >= float(min_fraction))
+    pk = valid.nonzero()                                        # the read-back that sizes E; row-major = (pair, cluster) order
+    if pk.shape[0] == 0:
+        return empty
+    p_of, k_of = pk[:, 0], pk[:, 1]
+    E = int(pk.shape[0])
+    est_frame, est_class, est_instance = frame_of[p_of], class_of[p_of], (k_of + 1).int()
+    ksets, kcounts = vote_sets_inst(pcld, kp_of, mask, inst, est_frame, est_class, est_instance)
+    kcenters, _, _, rounds = mean_shift(ksets, kcounts, radius, max_iter, sets_per_count=n_kps, want_labels=False)
+    if stats is not None:
+        stats["rounds_kps"], stats["counts_kps"] = rounds, kcounts
+    found = torch.cat([kcenters.view(E, n_kps, 3), centers[p_of, k_of].view(E, 1, 3)], dim=1)
+    cls_long = est_class.long()
+    model = torch.cat([mesh_kps[cls_long], mesh_ctr[cls_long].view(E, 1, 3)], dim=1)
+    T = best_fit_transform_batch(model, found) if use_ctr else best_fit_transform_batch(model[:, :n_kps], found[:, :n_kps])
+    return dict(est_RT=T, est_class=est_class, est_frame=est_frame, est_instance=est_instance, est_score=score[p_of, k_of],
+                kps=found, n_inside=n_in[p_of, k_of])
 
 
 def cal_frame_poses_lm(pcld, mask, ctr_of, pred_kp_of, use_ctr, n_cls, use_ctr_clus_flter, obj_id,

@@ -2,12 +2,13 @@
  * (SURVEY.md section 8f rank 2).  Replaces, batched over every (frame, object) pair at once:
  *
  *   MeanShiftTorch.fit          ffb6d/utils/meanshift_pytorch.py:27-58
+ *   MeanShiftTorch.fit_multi_clus                              :60-85
  *   best_fit_transform          ffb6d/utils/pvn3d_eval_utils_kpls.py:28-61
  *   the vote construction, mask selection and centre-cluster filtering of
  *   cal_frame_poses / cal_frame_poses_lm   ffb6d/utils/pvn3d_eval_utils_kpls.py:65-158,220-285
  *
  * All pointers are DEVICE pointers unless stated; every call is asynchronous on `stream`
- * except ffb6d_mean_shift_f32 with check_every > 0 (it polls a convergence flag).
+ * except ffb6d_mean_shift_f32 / ffb6d_mean_shift_multi_f32 with check_every > 0 (they poll a convergence flag).
  * Return value: 0 or an FFB6D_ERR_* code (text through ffb6d_last_error()).
  *
  * A "vote set" is a list of 3-D points stored as float4 {x, y, z, bit-cast int32 index of the
@@ -64,6 +65,52 @@ int ffb6d_mean_shift_f32(const float* sets, const int* counts, int sets_per_coun
                          int64_t set_stride, int64_t max_count, float bandwidth, int max_iter,
                          int check_every, float* centers, unsigned char* labels, int* n_inside,
                          int* iters, void* workspace, size_t workspace_bytes, ffb6d_stream_t stream);
+
+/* MeanShiftTorch.fit_multi_clus for G sets at once (meanshift_pytorch.py:60-85): the iteration of ffb6d_mean_shift_f32 (the same
+ * code in each of its forms), then one ball after another is peeled off the converged points instead of keeping the largest only.
+ * With C[0..M-1] the converged points of a set, h = bandwidth, K = max_clusters >= 1 and min_inside >= 1:
+ *   1. alive = all points, k = 0;
+ *   2. for every alive i: n_i = number of alive j with sqrtf(dx*dx + dy*dy + dz*dz) < h (the point itself counts);
+ *   3. winner w = the alive point with the largest n_i, lowest index on ties;
+ *   4. stop if no point is alive, or n_w < min_inside, or k == K;
+ *   5. k += 1; centre[k] = C[w], n_inside[k] = n_w; every alive j with |C_w - C_j| < h gets cluster[j] = k and leaves alive; to 2.
+ * Outputs, per set: n_clusters i32 [G] (<= K), centers f32 [G,K,3], n_inside i32 [G,K], cluster u8 [G,set_stride] (ids 1..;
+ * K <= 255).  Unused slots and points past the set's count are zero; points in no returned cluster have id 0.
+ *   - Cluster 1 is the single fit, as bits: its centre, n_inside and the membership cluster == 1 equal the centre, n_inside and
+ *     labels ffb6d_mean_shift_f32 returns for the same set and settings.
+ *   - The winners' sizes never increase from one peel to the next (a survivor's ball only loses members), so stopping at the
+ *     first n_w < min_inside is the same as filtering; min_inside = 1 and K >= M give the reference's full sequence.
+ *   - With a cap the result is the first K entries of that sequence.
+ * The ball sizes are counted once (one pass over the pairs of the distinct converged positions, weighted by multiplicity); every
+ * later peel subtracts the removed members from the sizes of the survivors.  Sizes are integers and the arg-max runs on a 64-bit
+ * (size << 32 | ~index) key: a set's result does not depend on the form that fitted it, on the other sets of the call or on
+ * what lies behind its count.  Arguments, workspace and asynchrony as ffb6d_mean_shift_f32 (no synchronisation beyond its own).
+ * Errors: FFB6D_ERR_ARG for max_clusters outside [1, 255] or min_inside < 1, FFB6D_ERR_WORKSPACE for a short workspace. */
+size_t ffb6d_mean_shift_multi_workspace_bytes(int G, int64_t set_stride);
+int ffb6d_mean_shift_multi_f32(const float* sets, const int* counts, int sets_per_count, int G,
+                               int64_t set_stride, int64_t max_count, float bandwidth, int max_iter,
+                               int check_every, int max_clusters, int min_inside, float* centers,
+                               unsigned char* cluster, int* n_inside, int* n_clusters, int* iters,
+                               void* workspace, size_t workspace_bytes, ffb6d_stream_t stream);
+
+/* Test hook: while `out` (f32 [G,set_stride,4], device) is set, ffb6d_mean_shift_multi_f32 also writes the converged point of
+ * every vote there ({x, y, z, the vote's own .w}) -- the C[] of the rule above, from whichever form fitted the set.  NULL
+ * (default) = off.  Process-wide, not thread-safe; for tests that hold the peel to a restatement on exactly these points. */
+void ffb6d_pose_set_converged_out(float* out);
+
+/* Instance map: inst[frame_of[p], idx] = cluster[p, j] for the j-th vote of set p (one centre-vote set per pair; the counterpart
+ * of ffb6d_set_labels_to_points).  Classes partition a frame's points and clusters partition a class's, so ONE u8 map [B,N]
+ * (0 = no instance, k = cluster id of the point's centre vote) serves every pair.  inst must be zero-initialised by the caller. */
+int ffb6d_set_clusters_to_points(const float* sets, const unsigned char* cluster, const int* counts,
+                                 const int* frame_of, int n_pairs, int64_t set_stride, int N,
+                                 unsigned char* inst, ffb6d_stream_t stream);
+
+/* ffb6d_vote_sets_f32 per instance: pair p = (frame_of[p], class_of[p], inst_of[p]) takes the points with
+ * mask == class_of[p] and inst == inst_of[p]; everything else as there. */
+int ffb6d_vote_sets_inst_f32(const float* pcld, const float* offsets, const void* mask, int mask_bits,
+                             const unsigned char* inst, const int* frame_of, const int* class_of,
+                             const int* inst_of, int n_pairs, int B, int S, int N, int64_t set_stride,
+                             float* sets, int* counts, ffb6d_stream_t stream);
 
 /* keep[frame_of[p], idx] = labels[p, j] for the j-th vote of set p (one set per pair): turns the
  * centre-cluster labels into a per-point filter for the keypoint votes (:131-134 / :270-273).
