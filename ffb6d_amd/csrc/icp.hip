@@ -13,6 +13,15 @@
 //                          the body of the keypoint fit), the bounding-box convergence test, the problem's state
 // A finished problem sets a flag that both kernels read first: no host polling, no read-back, the call never waits.
 //
+// Several instances of a class (the *_inst calls; the rule is in the header): problems are (frame, class, instance).
+//   map      icp_select_kernel<.., kInst> also tests the instance map; the loop is the one above on those sets
+//   nearest  the sets are the class's points; per iteration icp_correspond_kernel writes every problem's distances (stopped
+//            problems too: they go on competing under their pose), icp_claim_kernel -- one wavefront per (problem, 64 scene
+//            points), lane = scene point -- reads the rows of the problem's group (icp_groups_kernel: the run of adjacent
+//            problems with its frame and class), keeps the pairs the problem owns and makes the block's sums with the same
+//            butterfly; icp_solve_kernel is unchanged
+//   icp_inst_out_kernel writes the refined instance map from the kept pairs the loop left.
+//
 // Two forms of the search, identical results (the comparison is on (d2 bits, model index) as one 64-bit key, and a tile is
 // skipped only when its box is STRICTLY farther than the best distance; the box distance is rounded like the point distance,
 // so it never exceeds the distance of a point inside the box):
@@ -24,6 +33,7 @@
 //           of a block lie anywhere on the object (they are in cloud order).
 #include <algorithm>
 #include <cmath>
+#include <cstdint>
 #include <limits>
 #include <vector>
 
@@ -122,16 +132,50 @@ __device__ __forceinline__ unsigned long long visit_tile(const float4* __restric
     return wave_min_key(make_key(dist2(qx, qy, qz, m.x, m.y, m.z), m.w));
 }
 
+// The 17 sums of step 4 over a block of 64 scene points (lane = scene point, the whole wavefront calls): a kept lane adds its
+// pair (model point cloud[idx], scene point s, distance d2), the fixed butterfly adds the lanes, lane 0 stores.
+__device__ __forceinline__ void block_sums(bool kept, const float4* __restrict__ cloud, int idx, const float4 s, float d2, int lane,
+                                           double* __restrict__ out) {
+    double v[kSums];
+#pragma unroll
+    for (int k = 0; k < kSums; ++k) v[k] = 0.0;
+    if (kept) {
+        const float4 m = cloud[idx];
+        const double mm[3] = {m.x, m.y, m.z}, ss[3] = {s.x, s.y, s.z};
+        v[0] = 1.0;
+#pragma unroll
+        for (int r = 0; r < 3; ++r) {
+            v[1 + r] = mm[r];
+            v[4 + r] = ss[r];
+#pragma unroll
+            for (int c = 0; c < 3; ++c) v[7 + 3 * r + c] = mm[r] * ss[c];
+        }
+        v[16] = d2;
+    }
+#pragma unroll
+    for (int k = 0; k < kSums; ++k) {
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) v[k] += shfl_xor_f64(v[k], o);
+    }
+    if (lane == 0) {
+#pragma unroll
+        for (int k = 0; k < kSums; ++k) out[k] = v[k];
+    }
+}
+
 // ---- scene sets ------------------------------------------------------------------------------------------------------
-template <typename MaskT>
+// kInst: the map form of the instance calls -- a point is taken only when inst[frame, i] == inst_of[p] as well
+template <typename MaskT, bool kInst>
 __global__ __launch_bounds__(kBlock) void icp_select_kernel(
     const float* __restrict__ pcld, const MaskT* __restrict__ mask, const unsigned char* __restrict__ keep,
-    const int* __restrict__ frame_of, const int* __restrict__ class_of, int B, int N, int64_t stride, float4* __restrict__ sets,
-    int* __restrict__ counts) {
+    const unsigned char* __restrict__ inst, const int* __restrict__ frame_of, const int* __restrict__ class_of,
+    const int* __restrict__ inst_of, int B, int N, int64_t stride, float4* __restrict__ sets, int* __restrict__ counts) {
     __shared__ int wave_total[kBlock / 64];
     const int p = blockIdx.x;
     const int b = frame_of[p];
-    if (b < 0 || b >= B) {                                      // never an index: a problem without scene points
+    int want = 0;
+    if (kInst) want = inst_of[p];
+    if (b < 0 || b >= B || (kInst && (want < 1 || want > 255))) {      // never an index / an id: a problem without scene points
         if (threadIdx.x == 0) counts[p] = 0;
         return;
     }
@@ -142,6 +186,7 @@ __global__ __launch_bounds__(kBlock) void icp_select_kernel(
         const int i = i0 + threadIdx.x;
         bool sel = false;
         if (i < N) sel = mask[static_cast<int64_t>(b) * N + i] == cls && (!keep || keep[static_cast<int64_t>(b) * N + i]);
+        if (kInst && sel) sel = inst[static_cast<int64_t>(b) * N + i] == want;
         const unsigned long long bal = __ballot(sel);
         const int before = __popcll(bal & ((1ull << lane) - 1ull));
         __syncthreads();
@@ -310,32 +355,90 @@ __global__ __launch_bounds__(kBlock) void icp_correspond_kernel(const CorrArgs a
         if (a.d2_out) a.d2_out[at] = d2;
     }
     if (!a.partials) return;
-    double v[kSums];
-#pragma unroll
-    for (int k = 0; k < kSums; ++k) v[k] = 0.0;
-    if (kept) {
-        const float4 m = a.m.orig[ci.pt_begin + idx];
-        const double mm[3] = {m.x, m.y, m.z}, ss[3] = {s.x, s.y, s.z};
-        v[0] = 1.0;
-#pragma unroll
-        for (int r = 0; r < 3; ++r) {
-            v[1 + r] = mm[r];
-            v[4 + r] = ss[r];
-#pragma unroll
-            for (int c = 0; c < 3; ++c) v[7 + 3 * r + c] = mm[r] * ss[c];
+    block_sums(kept, a.m.orig + ci.pt_begin, idx, s, d2, lane, a.partials + (static_cast<int64_t>(p) * a.tiles + tile) * kSums);
+}
+
+// ---- nearest mode: the instances of a (frame, class) compete for every point ---------------------------------------------
+// group of p = the maximal run of adjacent problems with its frame and class: {begin, end} per problem, once per call
+__global__ __launch_bounds__(kBlock) void icp_groups_kernel(const int* __restrict__ frame_of, const int* __restrict__ class_of, int P, int nearest,
+                                                            int2* __restrict__ groups) {
+    const int p = blockIdx.x * kBlock + threadIdx.x;
+    if (p >= P) return;
+    int lo = p, hi = p + 1;
+    if (nearest) {
+        const int f = frame_of[p], c = class_of[p];
+        while (lo > 0 && frame_of[lo - 1] == f && class_of[lo - 1] == c) --lo;
+        while (hi < P && frame_of[hi] == f && class_of[hi] == c) ++hi;
+    }
+    int2 g;
+    g.x = lo;
+    g.y = hi;
+    groups[p] = g;
+}
+
+struct ClaimArgs {
+    const float4* sets;
+    const int* counts;
+    int64_t stride;
+    const int* class_of;
+    const int2* groups;
+    Prepared m;
+    int n_cls;
+    const float* d2_rows;                     // [P, stride] every problem's own smallest distance (icp_correspond_kernel)
+    const int* idx_rows;                      // [P, stride] its model point, -1 where its own gate drops the pair
+    int* idx_out;                             // or NULL; may be idx_rows
+    float* d2_out;                            // or NULL
+    int* owner_out;                           // or NULL
+    double* partials;                         // or NULL
+    int tiles;
+};
+
+// One wavefront per (problem, block of 64 scene points), lane = scene point: the rows of a group are aligned (its members have
+// the same scene set), so every member's distance to the lane's point is one coalesced read.  The owner is the member with the
+// smallest distance (float compare: a NaN never owns, the first of equals stays); the pair survives when p owns it.
+__global__ __launch_bounds__(64) void icp_claim_kernel(const ClaimArgs a) {
+    const int p = blockIdx.y, tile = blockIdx.x, lane = threadIdx.x;
+    const int cnt = a.counts[p];
+    const int q0 = tile * kTilePts;
+    if (q0 >= cnt) return;
+    const bool valid = q0 + lane < cnt;
+    const int64_t j = q0 + min(lane, cnt - 1 - q0);
+    const int2 g = a.groups[p];
+    int owner = -1;
+    float best = 0.f;
+    for (int q = g.x; q < g.y; ++q) {
+        const float d = a.d2_rows[static_cast<int64_t>(q) * a.stride + j];
+        if (d == d && (owner < 0 || d < best)) {
+            owner = q;
+            best = d;
         }
-        v[16] = d2;
     }
-#pragma unroll
-    for (int k = 0; k < kSums; ++k) {
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) v[k] += shfl_xor_f64(v[k], o);
+    const int64_t at = static_cast<int64_t>(p) * a.stride + j;
+    const int idx = a.idx_rows[at];
+    const float d2 = a.d2_rows[at];
+    const bool kept = valid && owner == p && idx >= 0;
+    if (valid) {
+        if (a.idx_out) a.idx_out[at] = kept ? idx : -1;
+        if (a.d2_out) a.d2_out[at] = d2;
+        if (a.owner_out) a.owner_out[at] = owner;
     }
-    if (lane == 0) {
-        double* out = a.partials + (static_cast<int64_t>(p) * a.tiles + tile) * kSums;
-#pragma unroll
-        for (int k = 0; k < kSums; ++k) out[k] = v[k];
-    }
+    if (!a.partials) return;
+    const int cls = a.class_of[p];
+    int pt_begin = 0;
+    if (cls >= 0 && cls < a.n_cls) pt_begin = a.m.cls[cls].pt_begin;
+    block_sums(kept, a.m.orig + pt_begin, idx, a.sets[at], d2, lane, a.partials + (static_cast<int64_t>(p) * a.tiles + tile) * kSums);
+}
+
+// inst_out[frame, i] = inst_of[p] for the kept pairs of the idx rows as the loop left them (one writer per point)
+__global__ __launch_bounds__(kBlock) void icp_inst_out_kernel(const float4* __restrict__ sets, const int* __restrict__ counts, int64_t stride,
+                                                              const int* __restrict__ idx_rows, const int* __restrict__ frame_of,
+                                                              const int* __restrict__ inst_of, int N, unsigned char* __restrict__ inst_out) {
+    const int p = blockIdx.y;
+    const int j = blockIdx.x * kBlock + threadIdx.x;
+    if (j >= counts[p]) return;                                 // (a frame that is no index has no scene points)
+    const int64_t at = static_cast<int64_t>(p) * stride + j;
+    if (idx_rows[at] < 0) return;
+    inst_out[static_cast<int64_t>(frame_of[p]) * N + __float_as_int(sets[at].w)] = static_cast<unsigned char>(inst_of[p]);
 }
 
 // ---- the update -----------------------------------------------------------------------------------------------------
@@ -419,21 +522,23 @@ struct Workspace {
     size_t state_off, state_bytes, bytes;
 };
 
+// (the offsets are added as integers: the layouts are also made on a null base, for the sizes alone)
+char* at_offset(void* base, size_t off) { return reinterpret_cast<char*>(reinterpret_cast<uintptr_t>(base) + off); }
+
 Workspace workspace_layout(void* base, int P, int64_t set_stride) {
     Workspace w;
-    char* b = static_cast<char*>(base);
     w.tiles = static_cast<int>(ceil_div(set_stride, kTilePts));
     size_t off = 0;
-    w.sets = reinterpret_cast<float4*>(b + off);
+    w.sets = reinterpret_cast<float4*>(at_offset(base, off));
     off += align256(sizeof(float4) * static_cast<size_t>(P) * set_stride);
-    w.counts = reinterpret_cast<int*>(b + off);
+    w.counts = reinterpret_cast<int*>(at_offset(base, off));
     off += align256(sizeof(int) * P);
-    w.partials = reinterpret_cast<double*>(b + off);
+    w.partials = reinterpret_cast<double*>(at_offset(base, off));
     off += align256(sizeof(double) * kSums * static_cast<size_t>(P) * w.tiles);
-    w.T = reinterpret_cast<double*>(b + off);
+    w.T = reinterpret_cast<double*>(at_offset(base, off));
     off += align256(sizeof(double) * 12 * P);
     w.state_off = off;
-    w.done = reinterpret_cast<int*>(b + off);
+    w.done = reinterpret_cast<int*>(at_offset(base, off));
     w.iters = w.done + P;
     w.n_pairs = w.iters + P;
     w.rms = reinterpret_cast<float*>(w.n_pairs + P);
@@ -460,7 +565,7 @@ unsigned morton10(unsigned x, unsigned y, unsigned z) {
 
 int check_scene_args(const char* who, const void* prepared, int n_cls, int64_t total, const void* pcld, const void* mask, int mask_bits,
                      const int* frame_of, const int* class_of, const double* T, int P, int B, int N, int64_t set_stride, float max_dist,
-                     void* workspace, size_t workspace_bytes) {
+                     void* workspace, size_t workspace_bytes, size_t need) {
     FFB6D_REQUIRE(P >= 0 && P <= 65535 && B > 0 && N > 0 && n_cls > 0 && total >= 0, "%s: bad sizes P=%d B=%d N=%d n_cls=%d total=%lld", who, P, B, N, n_cls,
                   (long long)total);
     FFB6D_REQUIRE(mask_bits == 32 || mask_bits == 64, "%s: mask_bits must be 32 or 64, got %d", who, mask_bits);
@@ -468,21 +573,60 @@ int check_scene_args(const char* who, const void* prepared, int n_cls, int64_t t
     FFB6D_REQUIRE(max_dist > 0.f, "%s: max_dist must be positive (inf allowed), got %g", who, (double)max_dist);
     if (P == 0) return 0;
     FFB6D_REQUIRE(prepared && pcld && mask && frame_of && class_of && T, "%s: null pointer", who);
-    const size_t need = ffb6d_icp_workspace_bytes(P, set_stride);
     if (!workspace || workspace_bytes < need)
         return ffb6d::set_error(FFB6D_ERR_WORKSPACE, "%s: workspace %zu < %zu bytes", who, workspace_bytes, need);
     return 0;
 }
 
-int launch_select(const float* pcld, const void* mask, int mask_bits, const unsigned char* keep, const int* frame_of, const int* class_of,
-                  int P, int B, int N, int64_t set_stride, const Workspace& w, hipStream_t st) {
-    if (mask_bits == 64)
-        icp_select_kernel<int64_t><<<static_cast<unsigned>(P), kBlock, 0, st>>>(pcld, static_cast<const int64_t*>(mask), keep, frame_of, class_of,
-                                                                                 B, N, set_stride, w.sets, w.counts);
+// inst / inst_of != NULL: the map form (mask == class && inst == inst_of[p])
+int launch_select(const float* pcld, const void* mask, int mask_bits, const unsigned char* keep, const unsigned char* inst, const int* frame_of,
+                  const int* class_of, const int* inst_of, int P, int B, int N, int64_t set_stride, const Workspace& w, hipStream_t st) {
+    const unsigned grid = static_cast<unsigned>(P);
+    if (mask_bits == 64 && inst)
+        icp_select_kernel<int64_t, true><<<grid, kBlock, 0, st>>>(pcld, static_cast<const int64_t*>(mask), keep, inst, frame_of, class_of, inst_of,
+                                                                   B, N, set_stride, w.sets, w.counts);
+    else if (mask_bits == 64)
+        icp_select_kernel<int64_t, false><<<grid, kBlock, 0, st>>>(pcld, static_cast<const int64_t*>(mask), keep, inst, frame_of, class_of, inst_of,
+                                                                    B, N, set_stride, w.sets, w.counts);
+    else if (inst)
+        icp_select_kernel<int32_t, true><<<grid, kBlock, 0, st>>>(pcld, static_cast<const int32_t*>(mask), keep, inst, frame_of, class_of, inst_of,
+                                                                   B, N, set_stride, w.sets, w.counts);
     else
-        icp_select_kernel<int32_t><<<static_cast<unsigned>(P), kBlock, 0, st>>>(pcld, static_cast<const int32_t*>(mask), keep, frame_of, class_of,
-                                                                                 B, N, set_stride, w.sets, w.counts);
+        icp_select_kernel<int32_t, false><<<grid, kBlock, 0, st>>>(pcld, static_cast<const int32_t*>(mask), keep, inst, frame_of, class_of, inst_of,
+                                                                    B, N, set_stride, w.sets, w.counts);
     FFB6D_LAUNCH_CHECK();
+    return 0;
+}
+
+// the instance calls: the workspace of the class calls, then the rows the owners are decided on and every problem's group
+struct InstWorkspace {
+    Workspace w;
+    int* idx_rows;                            // [P, set_stride]
+    float* d2_rows;                           // [P, set_stride]
+    int2* groups;                             // [P]
+    size_t bytes;
+};
+
+InstWorkspace inst_workspace_layout(void* base, int P, int64_t set_stride) {
+    InstWorkspace iw;
+    iw.w = workspace_layout(base, P, set_stride);
+    size_t off = iw.w.bytes;
+    iw.idx_rows = reinterpret_cast<int*>(at_offset(base, off));
+    off += align256(sizeof(int) * static_cast<size_t>(P) * set_stride);
+    iw.d2_rows = reinterpret_cast<float*>(at_offset(base, off));
+    off += align256(sizeof(float) * static_cast<size_t>(P) * set_stride);
+    iw.groups = reinterpret_cast<int2*>(at_offset(base, off));
+    off += align256(sizeof(int2) * P);
+    iw.bytes = off;
+    return iw;
+}
+
+// what the instance calls check before the checks they share with the class calls; each refusal has its own message
+int check_inst_args(const char* who, int P, int mode, const unsigned char* inst, const int* inst_of) {
+    FFB6D_REQUIRE(mode == 0 || mode == 1, "%s: mode must be 0 (map) or 1 (nearest), got %d", who, mode);
+    FFB6D_REQUIRE(P <= 65535, "%s: %d problems, at most 65535 to a call", who, P);
+    FFB6D_REQUIRE(mode == 1 || inst || P <= 0, "%s: the map mode needs the instance map (inst is NULL)", who);
+    FFB6D_REQUIRE(inst_of || P <= 0, "%s: null pointer (inst_of)", who);
     return 0;
 }
 
@@ -601,11 +745,11 @@ int ffb6d_icp_correspond_f32(const void* prepared, int n_cls, int64_t total, con
                              int64_t set_stride, float max_dist, int* idx, float* d2, int* counts, void* workspace, size_t workspace_bytes,
                              ffb6d_stream_t stream) {
     const int rc = check_scene_args("icp_correspond", prepared, n_cls, total, pcld, mask, mask_bits, frame_of, class_of, T, P, B, N, set_stride,
-                                    max_dist, workspace, workspace_bytes);
+                                    max_dist, workspace, workspace_bytes, ffb6d_icp_workspace_bytes(P, set_stride));
     if (rc != 0 || P == 0) return rc;
     hipStream_t st = ffb6d::as_stream(stream);
     const Workspace w = workspace_layout(workspace, P, set_stride);
-    const int rs = launch_select(pcld, mask, mask_bits, keep, frame_of, class_of, P, B, N, set_stride, w, st);
+    const int rs = launch_select(pcld, mask, mask_bits, keep, nullptr, frame_of, class_of, nullptr, P, B, N, set_stride, w, st);
     if (rs != 0) return rs;
     if (idx || d2) {
         const int64_t n = static_cast<int64_t>(P) * set_stride;
@@ -629,14 +773,14 @@ int ffb6d_icp_refine_f32(const void* prepared, int n_cls, int64_t total, const f
                          int* iters, void* workspace, size_t workspace_bytes, ffb6d_stream_t stream) {
     FFB6D_REQUIRE(max_iter >= 0 && tol >= 0.0 && min_pairs >= 1, "icp_refine: bad max_iter=%d / tol=%g / min_pairs=%d", max_iter, tol, min_pairs);
     const int rc = check_scene_args("icp_refine", prepared, n_cls, total, pcld, mask, mask_bits, frame_of, class_of, T0, P, B, N, set_stride,
-                                    max_dist, workspace, workspace_bytes);
+                                    max_dist, workspace, workspace_bytes, ffb6d_icp_workspace_bytes(P, set_stride));
     if (rc != 0 || P == 0) return rc;
     hipStream_t st = ffb6d::as_stream(stream);
     const Workspace w = workspace_layout(workspace, P, set_stride);
     FFB6D_HIP_TRY(hipMemsetAsync(static_cast<char*>(workspace) + w.state_off, 0, w.state_bytes, st));
     FFB6D_HIP_TRY(hipMemcpyAsync(w.T, T0, sizeof(double) * 12 * P, hipMemcpyDeviceToDevice, st));
     if (max_iter > 0) {
-        const int rs = launch_select(pcld, mask, mask_bits, keep, frame_of, class_of, P, B, N, set_stride, w, st);
+        const int rs = launch_select(pcld, mask, mask_bits, keep, nullptr, frame_of, class_of, nullptr, P, B, N, set_stride, w, st);
         if (rs != 0) return rs;
     }
     CorrArgs a;
@@ -651,6 +795,123 @@ int ffb6d_icp_refine_f32(const void* prepared, int n_cls, int64_t total, const f
         icp_correspond_kernel<<<dim3(static_cast<unsigned>(w.tiles), static_cast<unsigned>(P)), kBlock, 0, st>>>(a);
         FFB6D_LAUNCH_CHECK();
         icp_solve_kernel<<<static_cast<unsigned>(P), 64, 0, st>>>(s);
+        FFB6D_LAUNCH_CHECK();
+    }
+    if (T) FFB6D_HIP_TRY(hipMemcpyAsync(T, w.T, sizeof(double) * 12 * P, hipMemcpyDeviceToDevice, st));
+    if (n_pairs) FFB6D_HIP_TRY(hipMemcpyAsync(n_pairs, w.n_pairs, sizeof(int) * P, hipMemcpyDeviceToDevice, st));
+    if (rms) FFB6D_HIP_TRY(hipMemcpyAsync(rms, w.rms, sizeof(float) * P, hipMemcpyDeviceToDevice, st));
+    if (iters) FFB6D_HIP_TRY(hipMemcpyAsync(iters, w.iters, sizeof(int) * P, hipMemcpyDeviceToDevice, st));
+    return 0;
+}
+
+size_t ffb6d_icp_inst_workspace_bytes(int P, int64_t set_stride, int mode) {
+    if (P <= 0 || set_stride <= 0 || (mode != 0 && mode != 1)) return 0;
+    return inst_workspace_layout(nullptr, P, set_stride).bytes;
+}
+
+int ffb6d_icp_correspond_inst_f32(const void* prepared, int n_cls, int64_t total, const float* pcld, const void* mask, int mask_bits,
+                                  const unsigned char* keep, const unsigned char* inst, const int* frame_of, const int* class_of,
+                                  const int* inst_of, const double* T, int P, int B, int N, int64_t set_stride, float max_dist, int mode,
+                                  int* idx, float* d2, int* counts, int* owner, void* workspace, size_t workspace_bytes,
+                                  ffb6d_stream_t stream) {
+    int rc = check_inst_args("icp_correspond_inst", P, mode, inst, inst_of);
+    if (rc != 0) return rc;
+    rc = check_scene_args("icp_correspond_inst", prepared, n_cls, total, pcld, mask, mask_bits, frame_of, class_of, T, P, B, N, set_stride,
+                          max_dist, workspace, workspace_bytes, ffb6d_icp_inst_workspace_bytes(P, set_stride, mode));
+    if (rc != 0 || P == 0) return rc;
+    hipStream_t st = ffb6d::as_stream(stream);
+    const InstWorkspace iw = inst_workspace_layout(workspace, P, set_stride);
+    const Workspace& w = iw.w;
+    rc = launch_select(pcld, mask, mask_bits, keep, mode == 0 ? inst : nullptr, frame_of, class_of, mode == 0 ? inst_of : nullptr, P, B, N,
+                       set_stride, w, st);
+    if (rc != 0) return rc;
+    if (idx || d2 || owner) {
+        const int64_t n = static_cast<int64_t>(P) * set_stride;
+        const unsigned fill_grid = static_cast<unsigned>(ceil_div(n, kBlock));
+        if (idx || d2) {
+            icp_fill_kernel<<<fill_grid, kBlock, 0, st>>>(idx, d2, n);
+            FFB6D_LAUNCH_CHECK();
+        }
+        if (owner) {
+            icp_fill_kernel<<<fill_grid, kBlock, 0, st>>>(owner, nullptr, n);
+            FFB6D_LAUNCH_CHECK();
+        }
+        icp_groups_kernel<<<static_cast<unsigned>(ceil_div(P, kBlock)), kBlock, 0, st>>>(frame_of, class_of, P, mode, iw.groups);
+        FFB6D_LAUNCH_CHECK();
+        CorrArgs a;
+        a.sets = w.sets; a.counts = w.counts; a.stride = set_stride; a.class_of = class_of; a.T = T; a.done = nullptr;
+        a.m = prepared_view(prepared, prepared_layout(total, n_cls), n_cls);
+        a.n_cls = n_cls; a.max_d2 = max_dist * max_dist; a.form = g_form; a.idx_out = iw.idx_rows; a.d2_out = iw.d2_rows; a.partials = nullptr;
+        a.tiles = w.tiles; a.pairs = g_pairs;
+        const dim3 grid(static_cast<unsigned>(w.tiles), static_cast<unsigned>(P));
+        icp_correspond_kernel<<<grid, kBlock, 0, st>>>(a);
+        FFB6D_LAUNCH_CHECK();
+        ClaimArgs c;
+        c.sets = w.sets; c.counts = w.counts; c.stride = set_stride; c.class_of = class_of; c.groups = iw.groups; c.m = a.m; c.n_cls = n_cls;
+        c.d2_rows = iw.d2_rows; c.idx_rows = iw.idx_rows; c.idx_out = idx; c.d2_out = d2; c.owner_out = owner; c.partials = nullptr;
+        c.tiles = w.tiles;
+        icp_claim_kernel<<<grid, 64, 0, st>>>(c);
+        FFB6D_LAUNCH_CHECK();
+    }
+    if (counts) FFB6D_HIP_TRY(hipMemcpyAsync(counts, w.counts, sizeof(int) * P, hipMemcpyDeviceToDevice, st));
+    return 0;
+}
+
+int ffb6d_icp_refine_inst_f32(const void* prepared, int n_cls, int64_t total, const float* pcld, const void* mask, int mask_bits,
+                              const unsigned char* keep, const unsigned char* inst, const int* frame_of, const int* class_of,
+                              const int* inst_of, const double* T0, int P, int B, int N, int64_t set_stride, float max_dist, int max_iter,
+                              double tol, int min_pairs, int mode, double* T, int* n_pairs, float* rms, int* iters,
+                              unsigned char* inst_out, void* workspace, size_t workspace_bytes, ffb6d_stream_t stream) {
+    FFB6D_REQUIRE(max_iter >= 0 && tol >= 0.0 && min_pairs >= 1, "icp_refine_inst: bad max_iter=%d / tol=%g / min_pairs=%d", max_iter, tol,
+                  min_pairs);
+    int rc = check_inst_args("icp_refine_inst", P, mode, inst, inst_of);
+    if (rc != 0) return rc;
+    rc = check_scene_args("icp_refine_inst", prepared, n_cls, total, pcld, mask, mask_bits, frame_of, class_of, T0, P, B, N, set_stride,
+                          max_dist, workspace, workspace_bytes, ffb6d_icp_inst_workspace_bytes(P, set_stride, mode));
+    if (rc != 0) return rc;
+    hipStream_t st = ffb6d::as_stream(stream);
+    if (inst_out) FFB6D_HIP_TRY(hipMemsetAsync(inst_out, 0, static_cast<size_t>(B) * N, st));
+    if (P == 0) return 0;
+    const InstWorkspace iw = inst_workspace_layout(workspace, P, set_stride);
+    const Workspace& w = iw.w;
+    FFB6D_HIP_TRY(hipMemsetAsync(static_cast<char*>(workspace) + w.state_off, 0, w.state_bytes, st));
+    FFB6D_HIP_TRY(hipMemcpyAsync(w.T, T0, sizeof(double) * 12 * P, hipMemcpyDeviceToDevice, st));
+    if (max_iter > 0) {
+        rc = launch_select(pcld, mask, mask_bits, keep, mode == 0 ? inst : nullptr, frame_of, class_of, mode == 0 ? inst_of : nullptr, P, B, N,
+                           set_stride, w, st);
+        if (rc != 0) return rc;
+        icp_groups_kernel<<<static_cast<unsigned>(ceil_div(P, kBlock)), kBlock, 0, st>>>(frame_of, class_of, P, mode, iw.groups);
+        FFB6D_LAUNCH_CHECK();
+    }
+    // map: the loop of the class call on the instances' sets (the kept pairs go to the idx rows only when inst_out asks for them);
+    // nearest: every problem measures its distances in every iteration, stopped or not (it goes on competing under its pose), the
+    // claim kernel decides the owners and makes the sums, and the update is the class call's
+    CorrArgs a;
+    a.sets = w.sets; a.counts = w.counts; a.stride = set_stride; a.class_of = class_of; a.T = w.T; a.done = mode == 1 ? nullptr : w.done;
+    a.m = prepared_view(prepared, prepared_layout(total, n_cls), n_cls);
+    a.n_cls = n_cls; a.max_d2 = max_dist * max_dist; a.form = g_form; a.idx_out = (mode == 1 || inst_out) ? iw.idx_rows : nullptr;
+    a.d2_out = mode == 1 ? iw.d2_rows : nullptr; a.partials = mode == 1 ? nullptr : w.partials; a.tiles = w.tiles; a.pairs = g_pairs;
+    ClaimArgs c;
+    c.sets = w.sets; c.counts = w.counts; c.stride = set_stride; c.class_of = class_of; c.groups = iw.groups; c.m = a.m; c.n_cls = n_cls;
+    c.d2_rows = iw.d2_rows; c.idx_rows = iw.idx_rows; c.idx_out = iw.idx_rows; c.d2_out = nullptr; c.owner_out = nullptr;
+    c.partials = w.partials; c.tiles = w.tiles;
+    SolveArgs s;
+    s.counts = w.counts; s.class_of = class_of; s.m = a.m; s.n_cls = n_cls; s.partials = w.partials; s.tiles = w.tiles; s.T = w.T;
+    s.done = w.done; s.iters = w.iters; s.n_pairs = w.n_pairs; s.rms = w.rms; s.min_pairs = min_pairs; s.tol = tol;
+    const dim3 grid(static_cast<unsigned>(w.tiles), static_cast<unsigned>(P));
+    for (int it = 0; it < max_iter; ++it) {
+        icp_correspond_kernel<<<grid, kBlock, 0, st>>>(a);
+        FFB6D_LAUNCH_CHECK();
+        if (mode == 1) {
+            icp_claim_kernel<<<grid, 64, 0, st>>>(c);
+            FFB6D_LAUNCH_CHECK();
+        }
+        icp_solve_kernel<<<static_cast<unsigned>(P), 64, 0, st>>>(s);
+        FFB6D_LAUNCH_CHECK();
+    }
+    if (inst_out && max_iter > 0) {
+        icp_inst_out_kernel<<<dim3(static_cast<unsigned>(ceil_div(set_stride, kBlock)), static_cast<unsigned>(P)), kBlock, 0, st>>>(
+            w.sets, w.counts, set_stride, iw.idx_rows, frame_of, inst_of, N, inst_out);
         FFB6D_LAUNCH_CHECK();
     }
     if (T) FFB6D_HIP_TRY(hipMemcpyAsync(T, w.T, sizeof(double) * 12 * P, hipMemcpyDeviceToDevice, st));

@@ -30,17 +30,22 @@ class SensorToPose:
     fitted poses as the last step of stage C (on the pose side stream under the overlapped schedule).
     max_instances: None = one pose per (frame, class) through pose.solve_poses (above); an integer K = stage C is
     pose.solve_instances: up to K scored instances per (frame, class), `solve` then returns its dict of device tensors (the rows
-    bop.BOPSceneEval.add_batch takes).  Not with `refine` (ICP selects its scene points by class)."""
+    bop.BOPSceneEval.add_batch takes).  Not with `refine` (that ICP selects its scene points by class).
+    instance_refine: with max_instances only: the `refine` dict of pose.solve_instances_refined (models, mode="nearest" | "map",
+    max_iter, max_dist, ...): stage C is that function, instance-aware ICP as its last step, and `solve` returns its dict."""
 
     def __init__(self, net, K, n_points, mesh_kps, mesh_ctr, r_lst=None, classes=None, normals="depth", cam_scale=1.0,
-                 pose_inputs=None, seed=0, refine=None, max_instances=None):
+                 pose_inputs=None, seed=0, refine=None, max_instances=None, instance_refine=None):
         self.net, self.K, self.n_points = net, np.asarray(K, np.float64), int(n_points)
         self.mesh_kps, self.mesh_ctr, self.r_lst, self.classes = mesh_kps, mesh_ctr, r_lst, classes
         self.normals, self.cam_scale, self.pose_inputs, self.seed = normals, float(cam_scale), pose_inputs, int(seed)
         self.refine = refine
         if max_instances is not None and refine is not None:
             raise ValueError("max_instances and refine exclude each other: ICP refinement is defined for one instance per class")
+        if instance_refine is not None and max_instances is None:
+            raise ValueError("instance_refine needs max_instances (one pose per class is refined through `refine`)")
         self.max_instances = None if max_instances is None else int(max_instances)
+        self.instance_refine = instance_refine
         self.dev = next(net.parameters()).device
         self._streams = None
 
@@ -65,12 +70,15 @@ class SensorToPose:
 
     def solve(self, inp, out):
         """-> list over frames of (class ids, poses [n,3,4] float64, keypoints [n,n_kps+1,3]) (pose.solve_poses); with
-        max_instances the dict of pose.solve_instances"""
+        max_instances the dict of pose.solve_instances (of pose.solve_instances_refined with instance_refine)"""
         if self.pose_inputs is not None:
             pcld, mask, ctr_of, kp_of = self.pose_inputs(inp, out)
         else:
             pcld, mask = inp["cld"], out["pred_rgbd_segs"].argmax(dim=1)            # train_lm.py:385 / demo.py:160
             ctr_of, kp_of = out["pred_ctr_ofs"], out["pred_kp_ofs"]
+        if self.instance_refine is not None:
+            return _pose.solve_instances_refined(pcld, mask, ctr_of, kp_of, self.mesh_kps, self.mesh_ctr, self.max_instances,
+                                                 refine=self.instance_refine, classes=self.classes)
         if self.max_instances is not None:
             return _pose.solve_instances(pcld, mask, ctr_of, kp_of, self.mesh_kps, self.mesh_ctr, self.max_instances, classes=self.classes)
         return _pose.solve_poses(pcld, mask, ctr_of, kp_of, self.mesh_kps, self.mesh_ctr, r_lst=self.r_lst, classes=self.classes,

@@ -368,12 +368,46 @@ def solve_instances(pcld, mask, ctr_of, kp_of, mesh_kps, mesh_ctr, max_instances
     instance, in (0, 1]; the scores of a (frame, class) sum to at most 1.  Computed on the device.
     One read-back: the table of valid (pair, cluster) slots is turned into row indices (torch.nonzero), which sizes E -- after
     the centre pass, before the keypoint votes are gathered.  (classes=None reads the present classes back first, as solve_poses.)
-    Not done here, because both are tied to ONE instance per class: the cross-class centre mask filter (`refine_mask` of
-    solve_poses; ffb6d_refine_mask_by_center takes one centre per pair) and ICP refinement (`refine=`; refine.icp_refine selects
-    its scene points by class).  Passing either raises."""
+    Not done here, because solve_poses ties both to ONE instance per class: the cross-class centre mask filter (`refine_mask`;
+    one centre per pair) and ICP refinement (`refine=`; refine.icp_refine selects its scene points by class).  Passing either
+    raises; solve_instances_refined has the instance-aware form of both."""
     if unsupported:
         raise TypeError(f"solve_instances does not take {sorted(unsupported)}: the centre mask filter and ICP refinement are "
-                        "defined for one instance per class (use solve_poses)")
+                        "defined for one instance per class (use solve_poses, or solve_instances_refined)")
+    return _solve_instances(pcld, mask, ctr_of, kp_of, mesh_kps, mesh_ctr, max_instances, min_inside, min_fraction, classes, use_ctr,
+                            radius, max_iter, stats)
+
+
+def solve_instances_refined(pcld, mask, ctr_of, kp_of, mesh_kps, mesh_ctr, max_instances, refine=None, min_inside=1, min_fraction=0.0,
+                            classes=None, use_ctr=True, radius=RADIUS, max_iter=300, stats=None, refine_mask=False, r_lst=None):
+    """`solve_instances` with the two steps it leaves out, both instance-aware.  Arguments as solve_instances, and
+      refine: None, or dict(models=refine.PreparedModels, mode="nearest" | "map", max_iter=..., max_dist=..., [tol, min_pairs]):
+              the fitted poses go through ONE refine.icp_refine_instances call with the instance map the solver has ("nearest",
+              the default: the instances of a (frame, class) compete for every point of the class, also those whose centre vote
+              fell in no cluster; "map": every instance keeps the points of its centre cluster).  The keypoints stay as fitted.
+      refine_mask=True, r_lst: the cross-class centre mask filter of solve_poses (:83-108) with one row per centre cluster: a
+              first centre pass finds the clusters of the given mask, every foreground point goes to the class of the nearest
+              cluster centre within 0.8 radii, and the solver runs on that mask (ICP included).  The first pass sizes its rows
+              with a second read-back of the same kind as the one below (torch.nonzero on the table of valid slots).
+    Returns the dict of solve_instances with est_RT refined, and
+      est_RT_fit f64 [E,3,4] the fitted poses, icp_pairs i32 [E] / icp_rms f32 [E] / icp_iters i32 [E] (zero without `refine`),
+      inst u8 [B,N]: the instance map as ICP left it (refine.icp_refine_instances), or the centre-cluster map without `refine`.
+    est_score stays the vote share.  With `refine` no read-back is added to the one solve_instances makes."""
+    return _solve_instances(pcld, mask, ctr_of, kp_of, mesh_kps, mesh_ctr, max_instances, min_inside, min_fraction, classes, use_ctr,
+                            radius, max_iter, stats, refined=True, refine=refine, refine_mask=refine_mask, r_lst=r_lst)
+
+
+def _instance_rows(n_in, n_clus, counts, K, min_fraction):
+    """the valid (pair, cluster) slots as row indices, in (pair, cluster) order, and the scores [P,K]; torch.nonzero reads back"""
+    score = n_in.float() / counts.clamp(min=1).float()[:, None]
+    valid = (torch.arange(K, device=n_in.device)[None, :] < n_clus[:, None]) & (score >= float(min_fraction))
+    pk = valid.nonzero()
+    return pk[:, 0], pk[:, 1], score
+
+
+def _solve_instances(pcld, mask, ctr_of, kp_of, mesh_kps, mesh_ctr, max_instances, min_inside, min_fraction, classes, use_ctr, radius,
+                     max_iter, stats, refined=False, refine=None, refine_mask=False, r_lst=None):
+    """The body of solve_instances and solve_instances_refined (`refined`: the keys of the latter)."""
     _need_gpu(pcld, mask, ctr_of, kp_of)
     B, N, _ = pcld.shape
     n_kps = kp_of.shape[1]
@@ -389,11 +423,41 @@ def solve_instances(pcld, mask, ctr_of, kp_of, mesh_kps, mesh_ctr, max_instances
     empty = dict(est_RT=torch.zeros((0, 3, 4), dtype=torch.float64, device=dev), est_class=i32(0), est_frame=i32(0), est_instance=i32(0),
                  est_score=torch.zeros((0,), dtype=torch.float32, device=dev),
                  kps=torch.zeros((0, n_kps + 1, 3), dtype=torch.float32, device=dev), n_inside=i32(0))
+    if refined:
+        empty.update(est_RT_fit=empty["est_RT"], icp_pairs=i32(0), icp_rms=empty["est_score"], icp_iters=i32(0),
+                     inst=torch.zeros((B, N), dtype=torch.uint8, device=dev))
     if P == 0:
         return empty
     frame_of, class_of = _i32(frame_np, dev), _i32(class_np, dev)
     ctr_of = ctr_of.contiguous().float()
     pcld = pcld.contiguous().float()
+
+    if refine_mask:
+        # 0. the centre clusters of the given mask, one row each, decide the class of every foreground point
+        if r_lst is None:
+            raise ValueError("refine_mask needs r_lst (object radii, common.py:89-94)")
+        sets, counts = vote_sets(pcld, ctr_of, mask, frame_of, class_of)
+        centers, _, n_in, n_clus, rounds = mean_shift_multi(sets, counts, radius, K, min_inside, max_iter)
+        if stats is not None:
+            stats["rounds_refine"], stats["counts_refine"] = rounds, counts
+        p_of, k_of, _ = _instance_rows(n_in, n_clus, counts, K, min_fraction)
+        row_class = class_of[p_of]
+        per_frame = torch.zeros((B + 1,), dtype=torch.int64, device=dev)
+        per_frame.index_add_(0, frame_of[p_of].long() + 1, torch.ones_like(p_of))
+        row_begin = per_frame.cumsum(0).int()
+        if torch.is_tensor(r_lst) and r_lst.is_cuda:
+            row_dist = (r_lst.to(device=dev, dtype=torch.float64)[row_class.long() - 1] * 0.8).float()
+        else:
+            per_pair = torch.tensor([np.float32(float(r_lst[c - 1]) * 0.8) for c in class_np], dtype=torch.float32, device=dev)
+            row_dist = per_pair[p_of]
+        row_centers = centers[p_of, k_of].contiguous()
+        new_mask = torch.empty_like(mask)
+        with torch.cuda.device(dev):
+            rc = _lib.load().ffb6d_refine_mask_by_center(pcld.data_ptr(), ctr_of.data_ptr(), mask.data_ptr(), _mask_bits(mask),
+                                                         row_centers.data_ptr(), row_class.data_ptr(), row_begin.data_ptr(),
+                                                         row_dist.data_ptr(), B, N, new_mask.data_ptr(), _stream(pcld))
+        _lib.check(rc, "ffb6d_refine_mask_by_center")
+        mask = new_mask
 
     # 1. centre clusters of every (frame, class)
     sets, counts = vote_sets(pcld, ctr_of, mask, frame_of, class_of)
@@ -403,13 +467,10 @@ def solve_instances(pcld, mask, ctr_of, kp_of, mesh_kps, mesh_ctr, max_instances
     # 2. instance id of every point
     inst = instance_map(sets, cluster, counts, frame_of, B, N)
     # 3. one row per found instance (the sizes do not increase along k: the kept slots of a pair are a prefix)
-    score = n_in.float() / counts.clamp(min=1).float()[:, None]
-    valid = (torch.arange(K, device=dev)[None, :] < n_clus[:, None]) & (score >= float(min_fraction))
-    pk = valid.nonzero()                                        # the read-back that sizes E; row-major = (pair, cluster) order
-    if pk.shape[0] == 0:
-        return empty
-    p_of, k_of = pk[:, 0], pk[:, 1]
-    E = int(pk.shape[0])
+    p_of, k_of, score = _instance_rows(n_in, n_clus, counts, K, min_fraction)       # the read-back that sizes E
+    E = int(p_of.shape[0])
+    if E == 0:
+        return dict(empty, inst=inst) if refined else empty
     est_frame, est_class, est_instance = frame_of[p_of], class_of[p_of], (k_of + 1).int()
     ksets, kcounts = vote_sets_inst(pcld, kp_of, mask, inst, est_frame, est_class, est_instance)
     kcenters, _, _, rounds = mean_shift(ksets, kcounts, radius, max_iter, sets_per_count=n_kps, want_labels=False)
@@ -419,8 +480,18 @@ def solve_instances(pcld, mask, ctr_of, kp_of, mesh_kps, mesh_ctr, max_instances
     cls_long = est_class.long()
     model = torch.cat([mesh_kps[cls_long], mesh_ctr[cls_long].view(E, 1, 3)], dim=1)
     T = best_fit_transform_batch(model, found) if use_ctr else best_fit_transform_batch(model[:, :n_kps], found[:, :n_kps])
-    return dict(est_RT=T, est_class=est_class, est_frame=est_frame, est_instance=est_instance, est_score=score[p_of, k_of],
-                kps=found, n_inside=n_in[p_of, k_of])
+    out = dict(est_RT=T, est_class=est_class, est_frame=est_frame, est_instance=est_instance, est_score=score[p_of, k_of],
+               kps=found, n_inside=n_in[p_of, k_of])
+    if not refined:
+        return out
+    out.update(est_RT_fit=T, icp_pairs=i32(E), icp_rms=torch.zeros((E,), dtype=torch.float32, device=dev), icp_iters=i32(E), inst=inst)
+    if refine is not None:
+        from . import refine as _refine
+        opts = dict(refine)
+        opts.setdefault("mode", "nearest")
+        T, rstats = _refine.icp_refine_instances(pcld, mask, inst, T, est_frame, est_class, est_instance, opts.pop("models"), **opts)
+        out.update(est_RT=T, icp_pairs=rstats["n_pairs"], icp_rms=rstats["rms"], icp_iters=rstats["iters"], inst=rstats["inst"])
+    return out
 
 
 def cal_frame_poses_lm(pcld, mask, ctr_of, pred_kp_of, use_ctr, n_cls, use_ctr_clus_flter, obj_id,

@@ -132,3 +132,92 @@ def icp_refine(pcld, mask, poses, frame_of, class_of, models, max_iter=10, max_d
                                       ws.data_ptr(), wbytes, _stream(pcld))
     _lib.check(rc, "ffb6d_icp_refine_f32")
     return T, dict(n_pairs=n_pairs, rms=rms, iters=iters)
+
+
+# ---- several instances of a class in a frame ---------------------------------------------------------------------------
+MODES = {"map": 0, "nearest": 1}
+
+
+def _instance_problems(pcld, mask, inst, poses, frame_of, class_of, inst_of, models, mode, keep):
+    """_problems, and the instance map / the instance ids in the layout of the C ABI"""
+    if mode not in MODES:
+        raise ValueError(f"mode must be 'map' or 'nearest', got {mode!r}")
+    pcld, mask, poses, frame_of, class_of, keep, P = _problems(pcld, mask, poses, frame_of, class_of, models, keep)
+    if inst is None:
+        if mode == "map":
+            raise ValueError("mode 'map' needs the instance map `inst` (u8 [B,N])")
+    else:
+        _need_gpu(inst)
+        if inst.shape != mask.shape or inst.dtype != torch.uint8:
+            raise ValueError(f"inst must be uint8 {tuple(mask.shape)}, got {inst.dtype} {tuple(inst.shape)}")
+        inst = inst.contiguous()
+    if torch.is_tensor(inst_of):
+        _need_gpu(inst_of)
+    else:
+        inst_of = torch.as_tensor(np.asarray(inst_of, np.int32).reshape(-1))
+    inst_of = inst_of.to(device=pcld.device, dtype=torch.int32).reshape(-1).contiguous()
+    if int(inst_of.shape[0]) != P:
+        raise ValueError(f"{P} problems / {int(inst_of.shape[0])} instance ids")
+    return pcld, mask, inst, poses, frame_of, class_of, inst_of, keep, P
+
+
+def correspondences_instances(pcld, mask, inst, poses, frame_of, class_of, inst_of, models, mode="map", max_dist=float("inf"), keep=None):
+    """`correspondences` for problems (frame, class, instance) -- the rule is stated in include/ffb6d_refine.h.
+      inst u8 [B,N]: the instance map (pose.instance_map; 0 = no instance), inst_of [P] the problems' instance ids;
+      mode "map": the scene points of p are the class's points with inst == inst_of[p];
+      mode "nearest": they are all points of the class (inst may be None), and the adjacent problems of one (frame, class)
+           compete for each: the pair is kept only by the problem whose posed model is nearest.
+    -> idx i32 [P,N] (-1 where the pair is gated out, not owned, or j is beyond the count), d2 f32 [P,N] (the problem's own
+       smallest distance, owned or not), counts i32 [P], owner i32 [P,N] (index of the owning problem, -1 for none)."""
+    models = _prepared(models)
+    pcld, mask, inst, poses, frame_of, class_of, inst_of, keep, P = _instance_problems(pcld, mask, inst, poses, frame_of, class_of, inst_of,
+                                                                                       models, mode, keep)
+    B, N, _ = pcld.shape
+    dev = pcld.device
+    idx = torch.empty((P, N), dtype=torch.int32, device=dev)
+    d2 = torch.empty((P, N), dtype=torch.float32, device=dev)
+    counts = torch.empty((P,), dtype=torch.int32, device=dev)
+    owner = torch.empty((P, N), dtype=torch.int32, device=dev)
+    lib = _lib.load()
+    wbytes = lib.ffb6d_icp_inst_workspace_bytes(P, N, MODES[mode])
+    ws = torch.empty((max(wbytes, 1),), dtype=torch.uint8, device=dev)
+    with torch.cuda.device(dev), _lib.traced("icp_correspond_inst", 0, (P, N)):
+        rc = lib.ffb6d_icp_correspond_inst_f32(models.buf.data_ptr(), models.n_cls, models.total, pcld.data_ptr(), mask.data_ptr(),
+                                               _mask_bits(mask), keep.data_ptr() if keep is not None else None,
+                                               inst.data_ptr() if inst is not None else None, frame_of.data_ptr(), class_of.data_ptr(),
+                                               inst_of.data_ptr(), poses.data_ptr(), P, B, N, N, float(max_dist), MODES[mode],
+                                               idx.data_ptr(), d2.data_ptr(), counts.data_ptr(), owner.data_ptr(), ws.data_ptr(), wbytes,
+                                               _stream(pcld))
+    _lib.check(rc, "ffb6d_icp_correspond_inst_f32")
+    return idx, d2, counts, owner
+
+
+def icp_refine_instances(pcld, mask, inst, poses, frame_of, class_of, inst_of, models, mode="map", max_iter=10, max_dist=0.02, tol=0.0,
+                         min_pairs=3, keep=None):
+    """`icp_refine` for problems (frame, class, instance); inst / inst_of / mode as `correspondences_instances`.  In mode
+    "nearest" a problem that has stopped keeps its pose and goes on competing for points until the loop ends.
+    -> (poses f64 [P,3,4], dict n_pairs i32 [P], rms f32 [P], iters i32 [P], inst u8 [B,N]: the instance id of the problem that
+    kept the point's pair at the end, 0 elsewhere -- in mode "nearest" the refined instance map), all on the device; nothing is
+    read back."""
+    models = _prepared(models)
+    pcld, mask, inst, poses, frame_of, class_of, inst_of, keep, P = _instance_problems(pcld, mask, inst, poses, frame_of, class_of, inst_of,
+                                                                                       models, mode, keep)
+    B, N, _ = pcld.shape
+    dev = pcld.device
+    T = torch.empty((P, 3, 4), dtype=torch.float64, device=dev)
+    n_pairs = torch.empty((P,), dtype=torch.int32, device=dev)
+    rms = torch.empty((P,), dtype=torch.float32, device=dev)
+    iters = torch.empty((P,), dtype=torch.int32, device=dev)
+    inst_out = torch.empty((B, N), dtype=torch.uint8, device=dev)
+    lib = _lib.load()
+    wbytes = lib.ffb6d_icp_inst_workspace_bytes(P, N, MODES[mode])
+    ws = torch.empty((max(wbytes, 1),), dtype=torch.uint8, device=dev)
+    with torch.cuda.device(dev), _lib.traced("icp_refine_inst", 0, (P, N, int(max_iter))):
+        rc = lib.ffb6d_icp_refine_inst_f32(models.buf.data_ptr(), models.n_cls, models.total, pcld.data_ptr(), mask.data_ptr(),
+                                           _mask_bits(mask), keep.data_ptr() if keep is not None else None,
+                                           inst.data_ptr() if inst is not None else None, frame_of.data_ptr(), class_of.data_ptr(),
+                                           inst_of.data_ptr(), poses.data_ptr(), P, B, N, N, float(max_dist), int(max_iter), float(tol),
+                                           int(min_pairs), MODES[mode], T.data_ptr(), n_pairs.data_ptr(), rms.data_ptr(),
+                                           iters.data_ptr(), inst_out.data_ptr(), ws.data_ptr(), wbytes, _stream(pcld))
+    _lib.check(rc, "ffb6d_icp_refine_inst_f32")
+    return T, dict(n_pairs=n_pairs, rms=rms, iters=iters, inst=inst_out)

@@ -22,7 +22,33 @@
  * A class without model points, a class id outside [0, n_cls), a frame index outside [0, B) or an empty scene set
  * give a problem without pairs: its pose comes back as the bits that went in.
  *
- * All pointers are DEVICE pointers unless stated; ffb6d_icp_correspond_f32 and ffb6d_icp_refine_f32 enqueue their work
+ * Several instances of a class in a frame (ffb6d_icp_correspond_inst_f32, ffb6d_icp_refine_inst_f32).  Problem p becomes
+ * (frame_of[p], class_of[p], inst_of[p], T[p]); inst is the u8 [B,N] map of ffb6d_set_clusters_to_points
+ * (include/ffb6d_pose.h; 0 = no instance); tests/icp_inst_ref.py restates what follows.  Steps 1, 2, 4 and 5 are the
+ * ones above; the scene set and step 3 depend on `mode`:
+ *   mode 0, map.  The scene points are the points with mask == class && inst == inst_of[p] (and keep != 0 when given), in
+ *     index order.  Step 3 is unchanged.  An inst_of outside 1 .. 255 gives a problem without pairs: its pose comes back as
+ *     the bits that went in.
+ *   mode 1, nearest.  The scene points are the points with mask == class (and keep), in index order, whatever their
+ *     instance id (inst is not read and may be NULL; inst_of only names what is written to inst_out).
+ *     The GROUP of p is the maximal run of adjacent problems with the same frame_of and class_of (pose.solve_instances orders
+ *     its rows by (frame, class, instance), so its groups are the instances of a pair; equal pairs that are not adjacent form
+ *     separate groups).  After steps 1-2 of every problem of the group, the OWNER of scene point i is the group member with
+ *     the smallest d2: the comparison is in float32, a NaN distance never owns, equal distances go to the lowest problem
+ *     index.  Step 3 becomes: the pair is kept for p when p owns i AND d2 <= max_dist * max_dist.  A problem that has stopped
+ *     (step 5) keeps its pose and goes on competing under it until the loop ends.
+ * The sums of step 4 are made as above, per block of 64 scene points of the problem's set and added in block order, without
+ * atomics: a map-mode problem whose set equals a class problem's set gives that call's bits, and so does a nearest-mode
+ * problem alone in its group.
+ * inst_out u8 [B,N] (zeroed by the call, on the stream): inst_out[frame, i] = the low 8 bits of inst_of[p] where p keeps the
+ * pair of point i, 0 elsewhere.  Mode 0: the pairs p kept in the last iteration it made (a problem that stopped early: in
+ * that iteration, before its update).  Mode 1: the pairs kept in the loop's last iteration, iteration max_iter - 1, stopped
+ * problems included, under the poses that went into it; max_iter = 0 leaves it zero.  Within a group a point has one owner,
+ * and the sets of distinct map-mode problems are disjoint, so a point has one writer and no atomics are needed; problems that
+ * repeat a (frame, class, instance) in mode 0, or a (frame, class) in separate groups in mode 1, may keep the same point:
+ * it then carries the id of either.
+ *
+ * All pointers are DEVICE pointers unless stated; the ffb6d_icp_correspond* and ffb6d_icp_refine* calls enqueue their work
  * on `stream` and return without waiting for it or reading anything back.  Return value: 0 or an FFB6D_ERR_* code
  * (text through ffb6d_last_error()); on an error nothing is launched and no output is written.
  */
@@ -87,6 +113,32 @@ int ffb6d_icp_refine_f32(const void* prepared, int n_cls, int64_t total, const f
                          const double* T0, int P, int B, int N, int64_t set_stride, float max_dist, int max_iter,
                          double tol, int min_pairs, double* T, int* n_pairs, float* rms, int* iters, void* workspace,
                          size_t workspace_bytes, ffb6d_stream_t stream);
+
+/* The instance calls (the rule is stated at the top).  Arguments as the class calls, and:
+ *   inst u8 [B,N] (NULL allowed in mode 1 only); inst_of i32 [P]; mode 0 = map, 1 = nearest;
+ *   workspace of ffb6d_icp_inst_workspace_bytes(P, set_stride, mode) bytes (0 when P <= 0, set_stride <= 0 or mode is
+ *   neither): the class calls' workspace, one i32 and one f32 row of set_stride per problem, and the groups.
+ * ffb6d_icp_correspond_inst_f32, steps 1-3 once:
+ *   idx as ffb6d_icp_correspond_f32 with the mode's step 3: -1 where the pair is not kept, in mode 1 also where p does not
+ *   own the point;  d2 the problem's own smallest distance, owned or not;  counts the problem's scene points;
+ *   owner i32 [P,set_stride]: the index of the owning problem, -1 when no member of the group has a non-NaN distance or j is
+ *   beyond the count (all rows of a group agree; in mode 0 every problem is its own group).  Each may be NULL.
+ * ffb6d_icp_refine_inst_f32, the loop: T, n_pairs, rms, iters as ffb6d_icp_refine_f32; inst_out u8 [B,N] or NULL.
+ *   One launch for the scene sets, one for the groups, two per iteration in mode 0 and three in mode 1 (the distances of
+ *   every problem, the owners and sums, the updates), one for inst_out.
+ * Refused with their own messages: a mode outside {0, 1}, inst == NULL in mode 0, P > 65535. */
+size_t ffb6d_icp_inst_workspace_bytes(int P, int64_t set_stride, int mode);
+int ffb6d_icp_correspond_inst_f32(const void* prepared, int n_cls, int64_t total, const float* pcld, const void* mask,
+                                  int mask_bits, const unsigned char* keep, const unsigned char* inst, const int* frame_of,
+                                  const int* class_of, const int* inst_of, const double* T, int P, int B, int N,
+                                  int64_t set_stride, float max_dist, int mode, int* idx, float* d2, int* counts, int* owner,
+                                  void* workspace, size_t workspace_bytes, ffb6d_stream_t stream);
+int ffb6d_icp_refine_inst_f32(const void* prepared, int n_cls, int64_t total, const float* pcld, const void* mask,
+                              int mask_bits, const unsigned char* keep, const unsigned char* inst, const int* frame_of,
+                              const int* class_of, const int* inst_of, const double* T0, int P, int B, int N,
+                              int64_t set_stride, float max_dist, int max_iter, double tol, int min_pairs, int mode, double* T,
+                              int* n_pairs, float* rms, int* iters, unsigned char* inst_out, void* workspace,
+                              size_t workspace_bytes, ffb6d_stream_t stream);
 
 #ifdef __cplusplus
 }
