@@ -136,6 +136,9 @@ SIGNATURES = {
     # include/ffb6d_train.h
     "ffb6d_pose_targets": (_i32, [_vp, _vp, _i32, _vp, _i32, _vp, _vp, _i32, _vp, _vp, _i32, _i32, _i64, _i64, _i32, _i32, _vp,
                                   _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "ffb6d_pose_targets_inst_workspace_bytes": (_sz, [_i32, _i32]),
+    "ffb6d_pose_targets_inst": (_i32, [_vp, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i64, _i64, _i32, _i32, _vp, _vp,
+                                       _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "ffb6d_rgb_hsv_jitter": (_i32, [_vp, _vp, _vp, _i32, _i64, _i64, _vp]),
     "ffb6d_rgb_stencil": (_i32, [_vp, _vp, _c.c_uint64, _vp, _i32, _i64, _i64, _vp]),
     "ffb6d_add_real_back": (_i32, [_vp, _vp, _i32, _vp, _vp, _vp, _vp, _i32, _i32, _vp, _vp, _vp, _i32, _i64, _vp]),

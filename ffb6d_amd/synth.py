@@ -348,3 +348,76 @@ def sphere_mesh(subdiv, radius=0.1, seed=0):
     rng = np.random.RandomState(seed)
     xyz = (np.asarray(verts) * float(radius)).astype(np.float32)
     return dict(xyz=xyz, rgb=rng.randint(0, 256, (len(xyz), 3)).astype(np.uint8), faces=np.asarray(faces, np.int32))
+
+
+# ---- multi-instance scenes: several posed instances of a few asymmetric objects --------------------------------
+def bumpy_mesh(seed, radius=0.05, subdiv=2):
+    """An object without any symmetry, so that its pose is unambiguous: the icosphere of `sphere_mesh` scaled unequally along
+    its three axes (seeded, the longest half-axis = `radius` metres) with one bump, a seeded direction around which the surface
+    is pushed out by up to 35 %.  Same dict as sphere_mesh."""
+    rng = np.random.RandomState(seed + 4099)
+    m = sphere_mesh(subdiv, 1.0, seed=seed)
+    unit = m["xyz"].astype(np.float64)
+    scale = np.array([1.0, 0.55 + 0.2 * rng.rand(), 0.35 + 0.15 * rng.rand()])[rng.permutation(3)]
+    d = rng.randn(3)
+    d /= np.linalg.norm(d)
+    bump = 1.0 + 0.35 * np.clip((unit @ d - 0.6) / 0.4, 0.0, 1.0)
+    xyz = unit * scale * bump[:, None]
+    m["xyz"] = (xyz * (radius / np.linalg.norm(xyz, axis=1).max())).astype(np.float32)
+    return m
+
+
+def make_instance_scene(seed, instances=((1, 1, 1, 2), (1, 1)), n_classes=None, height=120, width=160, n_kps=8, radius=0.08,
+                        depth=(0.6, 0.8), bandwidth=0.04, overlap=False, K=None):
+    """A seeded scene with several instances of one class in a frame: what render.render / train_data.render_synthetic draw and
+    train_data.pose_targets_instances labels.  instances[b] lists the class ids (1 ..) of frame b's instances.
+      meshes     list by class id (None for class 0) of bumpy_mesh objects whose longest half-axis is `radius`
+      poses f64 [I,3,4], frame_of / class_of i32 [I]: the renderer's instance list, in the order of `instances`
+      K f64 [B,3,3]: the LineMOD intrinsics scaled to height x width (or the given [3,3])
+      mesh_kps f32 [n_cls,n_kps,3] seeded mesh vertices, mesh_ctr f32 [n_cls,3] the bounding-box centres, r_lst f32 [n_cls-1]
+      object radii, diameters f32 [n_cls] (index 0 unused, 1.0).
+    Placement (rejection sampling): rotations are uniform, centres lie at `depth` metres; the centres of two instances of a frame
+    are at least max(4 * bandwidth, 2 object radii) apart (4 bandwidths of the solver's mean shift, pose.RADIUS, keep their
+    centre clusters separate); every instance's bounding sphere projects inside the frame; and unless `overlap`, no two bounding
+    spheres of a frame overlap in the image, so that every instance is seen whole."""
+    rng = np.random.RandomState(seed)
+    B = len(instances)
+    n_cls = int(n_classes or max(max(f) for f in instances if len(f)) + 1)
+    meshes = [None] + [bumpy_mesh(seed * 31 + c, radius) for c in range(1, n_cls)]
+    if K is None:
+        K = LINEMOD_K * np.array([[width / 640.0], [height / 480.0], [1.0]])
+    K = np.asarray(K, np.float64)
+    mesh_kps, mesh_ctr = np.zeros((n_cls, n_kps, 3), np.float32), np.zeros((n_cls, 3), np.float32)
+    r_lst, diameters = np.zeros(n_cls - 1, np.float32), np.ones(n_cls, np.float32)
+    for c in range(1, n_cls):
+        v = meshes[c]["xyz"]
+        mesh_kps[c] = v[rng.choice(len(v), n_kps, replace=False)]
+        mesh_ctr[c] = (v.min(0) + v.max(0)) / 2
+        r_lst[c - 1] = np.linalg.norm(v, axis=1).max()
+        diameters[c] = 2 * r_lst[c - 1]
+    gap = max(4.0 * bandwidth, 2.0 * radius)
+    poses, frame_of, class_of = [], [], []
+    for b, classes in enumerate(instances):
+        placed = []
+        for c in classes:
+            for _ in range(10000):
+                z = rng.uniform(*depth)
+                u, v = rng.uniform(0, width), rng.uniform(0, height)
+                t = np.array([(u - K[0, 2]) * z / K[0, 0], (v - K[1, 2]) * z / K[1, 1], z])
+                r_px = max(K[0, 0], K[1, 1]) * radius / (z - radius)          # the bounding sphere's image radius, from above
+                inside = r_px <= u <= width - 1 - r_px and r_px <= v <= height - 1 - r_px
+                apart = all(np.linalg.norm(t - q) >= gap for q, _, _ in placed)
+                clear = overlap or all(np.hypot(u - uq, v - vq) >= r_px + rq for _, (uq, vq), rq in placed)
+                if inside and apart and clear:
+                    break
+            else:
+                raise ValueError(f"frame {b}: no room for {len(classes)} instances of radius {radius} in {height} x {width}")
+            placed.append((t, (u, v), r_px))
+            T = np.zeros((3, 4))
+            T[:, :3], T[:, 3] = random_rotation(rng), t
+            poses.append(T)
+            frame_of.append(b)
+            class_of.append(c)
+    return dict(meshes=meshes, poses=np.asarray(poses).reshape(-1, 3, 4), frame_of=np.asarray(frame_of, np.int32),
+                class_of=np.asarray(class_of, np.int32), K=np.stack([K] * B), mesh_kps=mesh_kps, mesh_ctr=mesh_ctr, r_lst=r_lst,
+                diameters=diameters, B=B, H=int(height), W=int(width))

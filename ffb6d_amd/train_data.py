@@ -2,6 +2,8 @@
 the C ABI of include/ffb6d_train.h.
 
     pose_targets            get_pose_gt_info + labels_pt   ycb_dataset.py:240,348-386, linemod_dataset.py:287,398-436
+    pose_targets_instances  the same per instance          several instances of one class in a frame, found through the renderer's
+                                                           instance image (no counterpart in the reference); votes_from_targets
     draw_noise_params       rgb_add_noise's host draws     ycb_dataset.py:107-143, linemod_dataset.py:142-164
     motion_blur_taps        linear_motion_blur's kernel    ycb_dataset.py:88-105 (cv2.line restated)
     rgb_add_noise           rgb_add_noise on the device    HSV, sharpen, motion blur, Gaussian blur, Gaussian noise
@@ -133,6 +135,91 @@ def pose_targets(cld, choose, label_img, cls_ids, RTs, mesh_kps, mesh_ctr):
                                     out["ctr_3ds"].data_ptr(), out["RTs"].data_ptr(), out["cls_ids"].data_ptr(), _stream(c))
     _lib.check(rc, "ffb6d_pose_targets")
     return out
+
+
+def _instance_ids(x, name, hi, dev):
+    """frame_of / class_of: host ids (checked against [0, hi)) or a device tensor (not read back) -> int32 [I] on dev."""
+    if torch.is_tensor(x) and x.is_cuda:
+        if x.dtype not in (torch.int32, torch.int64):
+            raise TypeError(f"{name} must be an integer tensor, got {x.dtype}")
+        return x.reshape(-1).to(torch.int32).contiguous()
+    a = np.asarray(x.detach().numpy() if torch.is_tensor(x) else x)
+    if a.size and a.dtype.kind not in "iu":
+        raise TypeError(f"{name} must hold integers, got {a.dtype}")
+    a = a.reshape(-1)
+    bad = (a < 0) | (a >= hi)
+    if bad.any():
+        i = int(np.argmax(bad))
+        raise ValueError(f"{name}[{i}] = {int(a[i])} outside [0, {hi})")
+    return torch.from_numpy(np.ascontiguousarray(a, np.int32)).to(dev)
+
+
+def pose_targets_instances(cld, choose, inst_img, frame_of, class_of, poses, mesh_kps, mesh_ctr):
+    """Targets of B frames per INSTANCE (include/ffb6d_train.h, ffb6d_pose_targets_inst, states the rule): a point's object is
+    the instance that owns its pixel in the renderer's `inst` image, so several instances of one class in a frame keep their
+    own keypoints, where pose_targets gives them all the last slot's.
+      cld f32 [B,N,3] (device); choose [B,N] or [B,1,N] int32 / int64 (device); inst_img int32 [B,H,W] (device): the global
+      instance index per pixel, negative = none (render.render(..., outputs=("inst",)));
+      frame_of / class_of [I], poses [I,3,4] float64: render's own instance list; mesh_kps [n_cls,K,3], mesh_ctr [n_cls,3].
+    The instance list and the meshes may be host data (uploaded) or device tensors.  Host frame ids outside [0, B) and class
+    ids outside [0, n_cls) raise ValueError before anything is launched; device ids are not read back (the kernel gives such
+    an instance zero rows and no point).  At most render.MAX_INSTANCES = 1024 instances, 64 keypoints.
+    Returns a dict of device tensors: labels i32 [B,N] (class), inst_of_point i32 [B,N] (-1 = none), kp_targ_ofst f32
+    [B,N,K,3] and ctr_targ_ofst f32 [B,N,3] (POINT MINUS KEYPOINT), kp_3ds f32 [I,K,3], ctr_3ds f32 [I,3], n_points i32 [I]
+    (sampled points owned by each instance).  Two launches, no read-back."""
+    _gpu(cld, choose, inst_img)
+    dev = cld.device
+    if cld.dim() != 3 or cld.shape[2] != 3 or cld.dtype != torch.float32:
+        raise TypeError(f"cld must be float32 [B,N,3], got {cld.dtype} {tuple(cld.shape)}")
+    B, N = int(cld.shape[0]), int(cld.shape[1])
+    ch = choose.reshape(B, -1) if choose.dim() == 3 else choose
+    if ch.dtype not in (torch.int32, torch.int64) or tuple(ch.shape) != (B, N):
+        raise TypeError(f"choose must be int32 / int64 [B,N] = [{B},{N}], got {choose.dtype} {tuple(choose.shape)}")
+    if inst_img.dtype != torch.int32 or inst_img.dim() != 3 or inst_img.shape[0] != B:
+        raise TypeError(f"inst_img must be int32 [B,H,W], got {inst_img.dtype} {tuple(inst_img.shape)}")
+    HW = int(inst_img.shape[1]) * int(inst_img.shape[2])
+    _, kps = _host_or_device(mesh_kps, dev, torch.float32)
+    _, ctr = _host_or_device(mesh_ctr, dev, torch.float32)
+    if kps.dim() != 3 or kps.shape[2] != 3 or tuple(ctr.shape) != (kps.shape[0], 3):
+        raise ValueError(f"mesh_kps must be [n_cls,K,3] and mesh_ctr [n_cls,3], got {tuple(kps.shape)}, {tuple(ctr.shape)}")
+    n_cls, K = int(kps.shape[0]), int(kps.shape[1])
+    frm = _instance_ids(frame_of, "frame_of", B, dev)
+    cls = _instance_ids(class_of, "class_of", n_cls, dev)
+    n_inst = int(frm.shape[0])
+    _, rts = _host_or_device(poses, dev, torch.float64)
+    rts = rts.reshape(-1, 3, 4)
+    if int(cls.shape[0]) != n_inst or int(rts.shape[0]) != n_inst:
+        raise ValueError(f"{n_inst} frames / {int(cls.shape[0])} classes / {int(rts.shape[0])} poses")
+    if not (1 <= K <= 64 and n_inst <= 1024):
+        raise ValueError(f"K = {K}, I = {n_inst} outside the kernel's limits (include/ffb6d_train.h)")
+    ch, img, c = ch.contiguous(), inst_img.contiguous(), cld.contiguous()
+    out = dict(labels=torch.empty((B, N), dtype=torch.int32, device=dev),
+               inst_of_point=torch.empty((B, N), dtype=torch.int32, device=dev),
+               kp_targ_ofst=torch.empty((B, N, K, 3), dtype=torch.float32, device=dev),
+               ctr_targ_ofst=torch.empty((B, N, 3), dtype=torch.float32, device=dev),
+               kp_3ds=torch.empty((n_inst, K, 3), dtype=torch.float32, device=dev),
+               ctr_3ds=torch.empty((n_inst, 3), dtype=torch.float32, device=dev),
+               n_points=torch.empty((n_inst,), dtype=torch.int32, device=dev))
+    lib = _lib.load()
+    need = int(lib.ffb6d_pose_targets_inst_workspace_bytes(n_inst, K))
+    ws = torch.empty((max(need, 1),), dtype=torch.uint8, device=dev)
+    with torch.cuda.device(dev), _lib.traced("pose_targets_inst", 4 * B * N * (3 * K + 9), (B, N, K, n_inst)):
+        rc = lib.ffb6d_pose_targets_inst(c.data_ptr(), ch.data_ptr(), int(ch.dtype == torch.int64), img.data_ptr(), frm.data_ptr(),
+                                         cls.data_ptr(), rts.data_ptr(), kps.data_ptr(), ctr.data_ptr(), n_cls, B, N, HW, n_inst, K,
+                                         out["labels"].data_ptr(), out["inst_of_point"].data_ptr(), out["kp_targ_ofst"].data_ptr(),
+                                         out["ctr_targ_ofst"].data_ptr(), out["kp_3ds"].data_ptr(), out["ctr_3ds"].data_ptr(),
+                                         out["n_points"].data_ptr(), ws.data_ptr(), need, _stream(c))
+    _lib.check(rc, "ffb6d_pose_targets_inst")
+    return out
+
+
+def votes_from_targets(targets):
+    """The targets of pose_targets / pose_targets_instances in the layout of the network's heads: (ctr_of f32 [B,1,N,3], kp_of
+    f32 [B,K,N,3]), the offsets a perfect network would emit.  Targets are POINT MINUS KEYPOINT and the solver votes
+    `pcld - offset` (pose.vote_sets; pvn3d_eval_utils_kpls.py:84,125: `pcld - ctr_of[0]`, `pcld - pred_kp_of`), so these votes
+    land on the posed keypoints up to one float rounding each way."""
+    kp, ctr = targets["kp_targ_ofst"], targets["ctr_targ_ofst"]
+    return ctr.unsqueeze(1).contiguous(), kp.permute(0, 2, 1, 3).contiguous()
 
 
 # ---------------------------------------------------------------------------------------------------------------------
@@ -504,7 +591,7 @@ def _sub(t, idx):
 def assemble_training_batch(rgb, depth, label_img, K, n_points, cls_ids, RTs, mesh_kps, mesh_ctr, cam_scale=1.0,
                             normals=None, synthetic=None, noise_params=None, back=None, second_noise_params=None,
                             flavour="ycb", composite_rgb=None, fill_missing=False, depth_to_mm=1.0, seed=None,
-                            aug_seed=None, generator=None, index_dtype=torch.int64, jitter_params=None):
+                            aug_seed=None, generator=None, index_dtype=torch.int64, jitter_params=None, instances=None):
     """Decoded training frames -> the network's inputs plus the loss's targets, all on the device.
       rgb uint8 [B,3,H,W], depth float32 [B,H,W] (raw units, metres = depth / cam_scale), label_img [B,H,W] uint8 / int32,
       K intrinsics, n_points; cls_ids / RTs / mesh_kps / mesh_ctr as in pose_targets.
@@ -517,8 +604,16 @@ def assemble_training_batch(rgb, depth, label_img, K, n_points, cls_ids, RTs, me
         frame, entries of non-synthetic frames are ignored.
       fill_missing: inputs.fill_missing(depth, cam_scale) afterwards (YCB, ycb_dataset.py:204).
       normals: [B,3,H,W] float32, or None = inputs.depth_normal(depth * depth_to_mm, fx, fy) (YCB: depth_to_mm = 0.1).
+      instances: None, or dict(inst_img=, frame_of=, class_of=, poses=) as pose_targets_instances takes them (what
+        render_synthetic(..., return_inst=True) drew from): frames with several instances of one class.  The targets then come
+        from pose_targets_instances; cls_ids and RTs are not used (pass None), and label_img stays the class image, which
+        the compositing reads.  add_real_back pastes the real frame only where that label is background and leaves label_img
+        itself alone, so the pixels an instance owns are the same before and after it: inst_img passes through untouched.
     Then the unchanged inputs.assemble_inputs (seed / generator: its sampling key; min_points=0) and pose_targets.
-    Returns the input dict plus labels, rgb_labels, RTs, kp_3ds, ctr_3ds, cls_ids, kp_targ_ofst, ctr_targ_ofst."""
+    Returns the input dict plus labels, rgb_labels, RTs, kp_3ds, ctr_3ds, cls_ids, kp_targ_ofst, ctr_targ_ofst.
+    With `instances`: the input dict plus labels, rgb_labels, kp_targ_ofst, ctr_targ_ofst, kp_3ds [I,K,3], ctr_3ds [I,3] (per
+    instance, not per slot), inst_labels i32 [B,N] (the instance of each point, -1 = none), n_points_inst i32 [I], and the
+    ground truth in the form bop.BOPSceneEval.add_batch takes: gt_RT f64 [I,3,4], gt_class / gt_frame i32 [I]."""
     _gpu(rgb, depth, label_img)
     B = int(rgb.shape[0])
     dev = rgb.device
@@ -549,9 +644,20 @@ def assemble_training_batch(rgb, depth, label_img, K, n_points, cls_ids, RTs, me
             normals = _inputs.depth_normal(depth * depth_to_mm, Kb[0, 0], Kb[1, 1])
     inp = _inputs.assemble_inputs(rgb, depth, normals, K, n_points, cam_scale=cam_scale, generator=generator,
                                   index_dtype=index_dtype, seed=seed, min_points=0)
-    tg = pose_targets(inp["cld_xyz0"], inp["choose"], label_img, cls_ids, RTs, mesh_kps, mesh_ctr)
     out = dict(inp)
-    out.update(tg)
+    if instances is None:
+        out.update(pose_targets(inp["cld_xyz0"], inp["choose"], label_img, cls_ids, RTs, mesh_kps, mesh_ctr))
+    else:
+        n_cls = len(mesh_kps)
+        gt_frame = _instance_ids(instances["frame_of"], "frame_of", B, dev)
+        gt_class = _instance_ids(instances["class_of"], "class_of", n_cls, dev)
+        _, gt_RT = _host_or_device(instances["poses"], dev, torch.float64)
+        gt_RT = gt_RT.reshape(-1, 3, 4)
+        tg = pose_targets_instances(inp["cld_xyz0"], inp["choose"], instances["inst_img"], gt_frame, gt_class, gt_RT, mesh_kps,
+                                    mesh_ctr)
+        out.update(tg, inst_labels=tg["inst_of_point"], n_points_inst=tg["n_points"], gt_RT=gt_RT, gt_class=gt_class,
+                   gt_frame=gt_frame)
+        del out["inst_of_point"], out["n_points"]
     out["rgb_labels"] = label_img.to(torch.int32)
     return out
 
@@ -559,15 +665,19 @@ def assemble_training_batch(rgb, depth, label_img, K, n_points, cls_ids, RTs, me
 # ---------------------------------------------------------------------------------------------------------------------
 # synthetic frames from meshes and poses
 # ---------------------------------------------------------------------------------------------------------------------
-def render_synthetic(meshes, poses, frame_of, class_of, K, B, H, W, depth_scale=1.0, min_visible=0):
+def render_synthetic(meshes, poses, frame_of, class_of, K, B, H, W, depth_scale=1.0, min_visible=0, return_inst=False):
     """The synthetic frames the reference reads from renders/ ("render": one instance per frame) and fuse/ ("fuse": several,
     occluding one another; linemod_dataset.py:209-249), drawn on the device from meshes and poses (ffb6d_amd/render.py):
       meshes: a render.PreparedMeshes (or its list); poses [I,3,4] (model -> camera, metres), frame_of / class_of [I], K.
     Returns (rgb uint8 [B,3,H,W], depth float32 [B,H,W] = metres * depth_scale (the raw units of a sensor whose cam_scale is
     depth_scale), label int32 [B,H,W] (class id, 0 = background), ok bool [I] = the instance owns at least min_visible pixels;
     the reference discards renders below 500, rgbd_rnder_sift_kp3ds.py:80): the rgb / depth / label_img that
-    assemble_training_batch(..., synthetic=...) takes."""
+    assemble_training_batch(..., synthetic=...) takes.
+    return_inst=True appends a fifth value, inst int32 [B,H,W]: the index into poses / frame_of / class_of of the instance that
+    owns each pixel, -1 = none -- the inst_img of pose_targets_instances and of assemble_training_batch(..., instances=...)."""
     from . import render as _render
-    out = _render.render(meshes, poses, frame_of, class_of, K, B, H, W, outputs=("rgb", "depth", "label", "visible"))
+    outputs = ("rgb", "depth", "label", "visible") + (("inst",) if return_inst else ())
+    out = _render.render(meshes, poses, frame_of, class_of, K, B, H, W, outputs=outputs)
     depth = out["depth"] if depth_scale == 1.0 else out["depth"] * float(depth_scale)
-    return out["rgb"], depth, out["label"], out["visible"] >= int(min_visible)
+    ret = (out["rgb"], depth, out["label"], out["visible"] >= int(min_visible))
+    return ret + (out["inst"],) if return_inst else ret

@@ -2,7 +2,8 @@
  * Dataset.get_item computes per frame on the CPU, batched on the device.
  *
  *   ffb6d_pose_targets        get_pose_gt_info + labels_pt   ycb_dataset.py:240,348-386, linemod_dataset.py:287,398-436
- *   ffb6d_rgb_hsv_jitter      rgb_add_noise, HSV stage       ycb_dataset.py:110-116, linemod_dataset.py:145-151
+ *   ffb6d_pose_targets_inst   the same per instance: several instances of one class in a frame (no counterpart in the reference)
+ *   ffb6d_rgb_hsv_jitter      rgb_add_noise, HSV stage      ycb_dataset.py:110-116, linemod_dataset.py:145-151
  *   ffb6d_rgb_stencil         rgb_add_noise, filter2D / GaussianBlur stages and the Gaussian noise
  *                                                             ycb_dataset.py:82-143, linemod_dataset.py:117-164
  *   ffb6d_add_real_back       add_real_back                  ycb_dataset.py:145-163, linemod_dataset.py:166-186
@@ -53,6 +54,49 @@ int ffb6d_pose_targets(const float* cld, const void* choose, int choose_i64, con
                        int n_cls, int B, int64_t N, int64_t HW, int O, int K, int* labels, float* kp_targ_ofst,
                        float* ctr_targ_ofst, float* kp_3ds, float* ctr_3ds, float* RTs_out, int* cls_ids_out,
                        ffb6d_stream_t stream);
+
+/* Pose targets per INSTANCE: B frames with N sampled points, I instances over the whole batch (the renderer's own list:
+ * ffb6d_render.h's frame_of / class_of / poses and its `inst` image) and K keypoints.  Where ffb6d_pose_targets finds a point's
+ * object through its class label -- so that two instances of one class in a frame both get the LAST slot's keypoints -- this call
+ * finds it through the instance image, and every instance keeps its own.
+ *   cld        f32 [B,N,3]             sampled points (metres)
+ *   choose     [B,N]  i32 or i64       (choose_i64 = 0 / 1) pixel indices into the HxW instance image, HW = H*W
+ *   inst_img   i32 [B,HW]              global instance index per pixel, negative = none
+ *   frame_of   i32 [I], class_of i32 [I]   frame and class of each instance
+ *   poses      f64 [I,3,4]             row-major [R|t] of each instance
+ *   mesh_kps   f32 [n_cls,K,3], mesh_ctr f32 [n_cls,3]   model-frame keypoints / centre indexed by class id
+ * Outputs:
+ *   labels     i32 [B,N], inst_of_point i32 [B,N]        class and global instance index per point (0 and -1 = none)
+ *   kp_targ_ofst  f32 [B,N,K,3], ctr_targ_ofst f32 [B,N,3]
+ *   kp_3ds     f32 [I,K,3], ctr_3ds f32 [I,3]            posed keypoints / centre per instance
+ *   n_points   i32 [I]                                   sampled points owned by each instance
+ * The rule:
+ *   instance i EXISTS iff 0 <= frame_of[i] < B and 1 <= class_of[i] < n_cls;
+ *   i = inst_img[b, choose[b,n]], none when the choose index lies outside [0, HW);
+ *   point n of frame b BELONGS to instance i iff 0 <= i < I, i exists and frame_of[i] == b (an index painted into another
+ *     frame's image than the instance's own owns nothing there);
+ *   a point that belongs:  labels = class_of[i], inst_of_point = i,
+ *     kp_targ_ofst[b,n,k,j] = (float)((double)cld[b,n,j] - kp3d[i,k,j])     POINT MINUS KEYPOINT, as ffb6d_pose_targets
+ *     ctr_targ_ofst[b,n,j]  = (float)((double)cld[b,n,j] - ctr3d[i,j])
+ *   any other point:  labels = 0, inst_of_point = -1, offsets all zero;
+ *   kp3d[i,k,j]  = ((m[k,0]*r[j,0] + m[k,1]*r[j,1]) + m[k,2]*r[j,2]) + t[j]   in double, m = mesh_kps[class_of[i]], r, t of poses[i]:
+ *   ctr3d[i,j]   = the same with m = mesh_ctr[class_of[i]]: exactly the formula of ffb6d_pose_targets, the same operations in the
+ *     same order with no contraction, so that with at most one instance per class and frame both calls give the same bits;
+ *   kp_3ds / ctr_3ds = (float)kp3d / (float)ctr3d; an instance that does not exist has zero rows and owns no point;
+ *   n_points[i] = the number of points that belong to i: an integer count, exact in whatever order it is added up; the call
+ *     zeroes it itself.
+ * Frame, class, instance and choose values are compared before they index anything: nothing is ever read or written through a bad
+ * id, whatever the device memory holds.  The Python wrapper rejects host-side ids out of range before launching.
+ * Two launches on `stream` (the instances' rows, then the points; one when I = 0 or there are no points), no read-back, no wait.
+ * The workspace (ffb6d_pose_targets_inst_workspace_bytes: the double rows of all instances, 0 for I = 0) may hold anything on entry.
+ * Limits: 1 <= K <= 64, 0 <= I <= 1024.  FFB6D_ERR_ARG, with nothing launched or written: negative sizes, n_cls < 1, K or I outside
+ * the limits, a null pointer that would be used, B > 65535; FFB6D_ERR_WORKSPACE: a workspace below the query, or not 8-byte aligned. */
+size_t ffb6d_pose_targets_inst_workspace_bytes(int I, int K);
+int ffb6d_pose_targets_inst(const float* cld, const void* choose, int choose_i64, const int* inst_img, const int* frame_of,
+                            const int* class_of, const double* poses, const float* mesh_kps, const float* mesh_ctr, int n_cls,
+                            int B, int64_t N, int64_t HW, int I, int K, int* labels, int* inst_of_point, float* kp_targ_ofst,
+                            float* ctr_targ_ofst, float* kp_3ds, float* ctr_3ds, int* n_points, void* workspace,
+                            size_t workspace_bytes, ffb6d_stream_t stream);
 
 /* HSV jitter of B uint8 images [B,3,H,W] (plane 0 plays OpenCV's "B": the reference hands an RGB array to
  * COLOR_BGR2HSV / COLOR_HSV2BGR, ycb :111,116).  fs_fv f64 [B,2]; a frame with fs_fv[b,0] < 0 is copied unchanged.
