@@ -630,6 +630,32 @@ int check_inst_args(const char* who, int P, int mode, const unsigned char* inst,
     return 0;
 }
 
+// what differs between the calls: the poses they measure under (T, done) and where the results go (rows, partial sums)
+CorrArgs make_corr_args(const Workspace& w, int64_t set_stride, const int* class_of, const double* T, const int* done, const void* prepared,
+                        int64_t total, int n_cls, float max_dist, int* idx_out, float* d2_out, double* partials) {
+    CorrArgs a;
+    a.sets = w.sets; a.counts = w.counts; a.stride = set_stride; a.class_of = class_of; a.T = T; a.done = done;
+    a.m = prepared_view(prepared, prepared_layout(total, n_cls), n_cls);
+    a.n_cls = n_cls; a.max_d2 = max_dist * max_dist; a.form = g_form; a.idx_out = idx_out; a.d2_out = d2_out; a.partials = partials;
+    a.tiles = w.tiles; a.pairs = g_pairs;
+    return a;
+}
+
+SolveArgs make_solve_args(const Workspace& w, const int* class_of, const Prepared& m, int n_cls, int min_pairs, double tol) {
+    SolveArgs s;
+    s.counts = w.counts; s.class_of = class_of; s.m = m; s.n_cls = n_cls; s.partials = w.partials; s.tiles = w.tiles; s.T = w.T;
+    s.done = w.done; s.iters = w.iters; s.n_pairs = w.n_pairs; s.rms = w.rms; s.min_pairs = min_pairs; s.tol = tol;
+    return s;
+}
+
+int copy_results(const Workspace& w, int P, double* T, int* n_pairs, float* rms, int* iters, hipStream_t st) {
+    if (T) FFB6D_HIP_TRY(hipMemcpyAsync(T, w.T, sizeof(double) * 12 * P, hipMemcpyDeviceToDevice, st));
+    if (n_pairs) FFB6D_HIP_TRY(hipMemcpyAsync(n_pairs, w.n_pairs, sizeof(int) * P, hipMemcpyDeviceToDevice, st));
+    if (rms) FFB6D_HIP_TRY(hipMemcpyAsync(rms, w.rms, sizeof(float) * P, hipMemcpyDeviceToDevice, st));
+    if (iters) FFB6D_HIP_TRY(hipMemcpyAsync(iters, w.iters, sizeof(int) * P, hipMemcpyDeviceToDevice, st));
+    return 0;
+}
+
 }  // namespace
 
 extern "C" {
@@ -755,11 +781,7 @@ int ffb6d_icp_correspond_f32(const void* prepared, int n_cls, int64_t total, con
         const int64_t n = static_cast<int64_t>(P) * set_stride;
         icp_fill_kernel<<<static_cast<unsigned>(ceil_div(n, kBlock)), kBlock, 0, st>>>(idx, d2, n);
         FFB6D_LAUNCH_CHECK();
-        CorrArgs a;
-        a.sets = w.sets; a.counts = w.counts; a.stride = set_stride; a.class_of = class_of; a.T = T; a.done = nullptr;
-        a.m = prepared_view(prepared, prepared_layout(total, n_cls), n_cls);
-        a.n_cls = n_cls; a.max_d2 = max_dist * max_dist; a.form = g_form; a.idx_out = idx; a.d2_out = d2; a.partials = nullptr;
-        a.tiles = w.tiles; a.pairs = g_pairs;
+        const CorrArgs a = make_corr_args(w, set_stride, class_of, T, nullptr, prepared, total, n_cls, max_dist, idx, d2, nullptr);
         icp_correspond_kernel<<<dim3(static_cast<unsigned>(w.tiles), static_cast<unsigned>(P)), kBlock, 0, st>>>(a);
         FFB6D_LAUNCH_CHECK();
     }
@@ -783,25 +805,15 @@ int ffb6d_icp_refine_f32(const void* prepared, int n_cls, int64_t total, const f
         const int rs = launch_select(pcld, mask, mask_bits, keep, nullptr, frame_of, class_of, nullptr, P, B, N, set_stride, w, st);
         if (rs != 0) return rs;
     }
-    CorrArgs a;
-    a.sets = w.sets; a.counts = w.counts; a.stride = set_stride; a.class_of = class_of; a.T = w.T; a.done = w.done;
-    a.m = prepared_view(prepared, prepared_layout(total, n_cls), n_cls);
-    a.n_cls = n_cls; a.max_d2 = max_dist * max_dist; a.form = g_form; a.idx_out = nullptr; a.d2_out = nullptr; a.partials = w.partials;
-    a.tiles = w.tiles; a.pairs = g_pairs;
-    SolveArgs s;
-    s.counts = w.counts; s.class_of = class_of; s.m = a.m; s.n_cls = n_cls; s.partials = w.partials; s.tiles = w.tiles; s.T = w.T;
-    s.done = w.done; s.iters = w.iters; s.n_pairs = w.n_pairs; s.rms = w.rms; s.min_pairs = min_pairs; s.tol = tol;
+    const CorrArgs a = make_corr_args(w, set_stride, class_of, w.T, w.done, prepared, total, n_cls, max_dist, nullptr, nullptr, w.partials);
+    const SolveArgs s = make_solve_args(w, class_of, a.m, n_cls, min_pairs, tol);
     for (int it = 0; it < max_iter; ++it) {
         icp_correspond_kernel<<<dim3(static_cast<unsigned>(w.tiles), static_cast<unsigned>(P)), kBlock, 0, st>>>(a);
         FFB6D_LAUNCH_CHECK();
         icp_solve_kernel<<<static_cast<unsigned>(P), 64, 0, st>>>(s);
         FFB6D_LAUNCH_CHECK();
     }
-    if (T) FFB6D_HIP_TRY(hipMemcpyAsync(T, w.T, sizeof(double) * 12 * P, hipMemcpyDeviceToDevice, st));
-    if (n_pairs) FFB6D_HIP_TRY(hipMemcpyAsync(n_pairs, w.n_pairs, sizeof(int) * P, hipMemcpyDeviceToDevice, st));
-    if (rms) FFB6D_HIP_TRY(hipMemcpyAsync(rms, w.rms, sizeof(float) * P, hipMemcpyDeviceToDevice, st));
-    if (iters) FFB6D_HIP_TRY(hipMemcpyAsync(iters, w.iters, sizeof(int) * P, hipMemcpyDeviceToDevice, st));
-    return 0;
+    return copy_results(w, P, T, n_pairs, rms, iters, st);
 }
 
 size_t ffb6d_icp_inst_workspace_bytes(int P, int64_t set_stride, int mode) {
@@ -838,11 +850,7 @@ int ffb6d_icp_correspond_inst_f32(const void* prepared, int n_cls, int64_t total
         }
         icp_groups_kernel<<<static_cast<unsigned>(ceil_div(P, kBlock)), kBlock, 0, st>>>(frame_of, class_of, P, mode, iw.groups);
         FFB6D_LAUNCH_CHECK();
-        CorrArgs a;
-        a.sets = w.sets; a.counts = w.counts; a.stride = set_stride; a.class_of = class_of; a.T = T; a.done = nullptr;
-        a.m = prepared_view(prepared, prepared_layout(total, n_cls), n_cls);
-        a.n_cls = n_cls; a.max_d2 = max_dist * max_dist; a.form = g_form; a.idx_out = iw.idx_rows; a.d2_out = iw.d2_rows; a.partials = nullptr;
-        a.tiles = w.tiles; a.pairs = g_pairs;
+        const CorrArgs a = make_corr_args(w, set_stride, class_of, T, nullptr, prepared, total, n_cls, max_dist, iw.idx_rows, iw.d2_rows, nullptr);
         const dim3 grid(static_cast<unsigned>(w.tiles), static_cast<unsigned>(P));
         icp_correspond_kernel<<<grid, kBlock, 0, st>>>(a);
         FFB6D_LAUNCH_CHECK();
@@ -886,18 +894,15 @@ int ffb6d_icp_refine_inst_f32(const void* prepared, int n_cls, int64_t total, co
     // map: the loop of the class call on the instances' sets (the kept pairs go to the idx rows only when inst_out asks for them);
     // nearest: every problem measures its distances in every iteration, stopped or not (it goes on competing under its pose), the
     // claim kernel decides the owners and makes the sums, and the update is the class call's
-    CorrArgs a;
-    a.sets = w.sets; a.counts = w.counts; a.stride = set_stride; a.class_of = class_of; a.T = w.T; a.done = mode == 1 ? nullptr : w.done;
-    a.m = prepared_view(prepared, prepared_layout(total, n_cls), n_cls);
-    a.n_cls = n_cls; a.max_d2 = max_dist * max_dist; a.form = g_form; a.idx_out = (mode == 1 || inst_out) ? iw.idx_rows : nullptr;
-    a.d2_out = mode == 1 ? iw.d2_rows : nullptr; a.partials = mode == 1 ? nullptr : w.partials; a.tiles = w.tiles; a.pairs = g_pairs;
+    const bool nearest = mode == 1;
+    const CorrArgs a = make_corr_args(w, set_stride, class_of, w.T, nearest ? nullptr : w.done, prepared, total, n_cls, max_dist,
+                                      (nearest || inst_out) ? iw.idx_rows : nullptr, nearest ? iw.d2_rows : nullptr,
+                                      nearest ? nullptr : w.partials);
     ClaimArgs c;
     c.sets = w.sets; c.counts = w.counts; c.stride = set_stride; c.class_of = class_of; c.groups = iw.groups; c.m = a.m; c.n_cls = n_cls;
     c.d2_rows = iw.d2_rows; c.idx_rows = iw.idx_rows; c.idx_out = iw.idx_rows; c.d2_out = nullptr; c.owner_out = nullptr;
     c.partials = w.partials; c.tiles = w.tiles;
-    SolveArgs s;
-    s.counts = w.counts; s.class_of = class_of; s.m = a.m; s.n_cls = n_cls; s.partials = w.partials; s.tiles = w.tiles; s.T = w.T;
-    s.done = w.done; s.iters = w.iters; s.n_pairs = w.n_pairs; s.rms = w.rms; s.min_pairs = min_pairs; s.tol = tol;
+    const SolveArgs s = make_solve_args(w, class_of, a.m, n_cls, min_pairs, tol);
     const dim3 grid(static_cast<unsigned>(w.tiles), static_cast<unsigned>(P));
     for (int it = 0; it < max_iter; ++it) {
         icp_correspond_kernel<<<grid, kBlock, 0, st>>>(a);
@@ -914,11 +919,7 @@ int ffb6d_icp_refine_inst_f32(const void* prepared, int n_cls, int64_t total, co
             w.sets, w.counts, set_stride, iw.idx_rows, frame_of, inst_of, N, inst_out);
         FFB6D_LAUNCH_CHECK();
     }
-    if (T) FFB6D_HIP_TRY(hipMemcpyAsync(T, w.T, sizeof(double) * 12 * P, hipMemcpyDeviceToDevice, st));
-    if (n_pairs) FFB6D_HIP_TRY(hipMemcpyAsync(n_pairs, w.n_pairs, sizeof(int) * P, hipMemcpyDeviceToDevice, st));
-    if (rms) FFB6D_HIP_TRY(hipMemcpyAsync(rms, w.rms, sizeof(float) * P, hipMemcpyDeviceToDevice, st));
-    if (iters) FFB6D_HIP_TRY(hipMemcpyAsync(iters, w.iters, sizeof(int) * P, hipMemcpyDeviceToDevice, st));
-    return 0;
+    return copy_results(w, P, T, n_pairs, rms, iters, st);
 }
 
 }  // extern "C"

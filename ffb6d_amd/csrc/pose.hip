@@ -1103,15 +1103,6 @@ int ffb6d_vote_sets_inst_f32(const float* pcld, const float* offsets, const void
                          inst, inst_of);
 }
 
-size_t ffb6d_mean_shift_workspace_bytes(int G, int64_t set_stride) {
-    if (G <= 0 || set_stride <= 0) return 0;
-    // two position buffers, the tail of the round-by-round path (shift, rounds, best), and for the chip-wide rounds of the sets beyond
-    // the one-workgroup fit: representative and owner maps (u32 per point each) + five ints per set
-    return 2 * align256(static_cast<size_t>(G) * set_stride * sizeof(float4)) + align256(3 * sizeof(unsigned) * G) +
-           align256(sizeof(int) * G) + align256(sizeof(unsigned long long) * G) +
-           2 * align256(static_cast<size_t>(G) * set_stride * sizeof(unsigned)) + align256(5 * sizeof(int) * G);
-}
-
 }  // extern "C"
 
 // test hook (ffb6d_pose_set_converged_out)
@@ -1119,276 +1110,331 @@ static float4* g_converged_out = nullptr;
 
 namespace {
 
-// ffb6d_mean_shift_multi_f32: K > 0 selects the peeling tails; centers [G,K,3], labels = cluster u8 [G,stride], n_inside [G,K]
-struct MultiArgs {
-    int K = 0, min_inside = 1;
-    int* n_clusters = nullptr;
-    float4* conv = nullptr;                                     // test hook: converged position of every point, [G,stride]
+// ---- mean shift, host side: one workspace layout, the switches of one call, the fit launch, then the phases in their order ----
+struct MeanShiftWorkspace {
+    float4 *buf0, *buf1;                      // [G,stride] each: positions, ping-pong
+    unsigned* shift;                          // [3,G] largest move of a round (slot t % 3); the spread rounds use slots 0 and 1
+    int* rounds;                              // [G]
+    unsigned long long* best;                 // [G] winning ball of the round-by-round path
+    unsigned *rep, *owner;                    // [G,stride] each: maps of the chip-wide rounds
+    int *big_ids, *len_of, *state_of;         // [G] each; len_of | state_of are adjacent so that one copy reads both
+    unsigned* move_of;                        // [G], then
+    int* dups_of;                             // [G]
+    size_t tail_bytes, big_bytes, bytes;      // cleared per call: shift .. best; before the chip-wide rounds: big_ids .. dups_of
+    // memory that is dead when its second user comes
+    int* n_large() const { return reinterpret_cast<int*>(best); }                          // `best` is cleared again before the round-by-round path
+    unsigned char* fit_labels() const { return reinterpret_cast<unsigned char*>(rep); }    // the continued fits come after the last chip-wide round
+    int* peel_sizes() const { return reinterpret_cast<int*>(rep); }                        // the peel comes after everything that reads the maps
+    unsigned* peel_removed() const { return owner; }
 };
 
-// the four instantiations of the one-workgroup fit behind one launch
-struct FitLaunch {
+MeanShiftWorkspace mean_shift_layout(void* base, int G, int64_t set_stride) {
+    MeanShiftWorkspace w;
+    const size_t points = static_cast<size_t>(G) * set_stride;
+    size_t off = 0;                           // (added as an integer: the layout is also made on a null base, for the size alone)
+    auto take = [&](size_t n) { off += align256(n); return reinterpret_cast<uintptr_t>(base) + off - align256(n); };
+    w.buf0 = reinterpret_cast<float4*>(take(points * sizeof(float4)));
+    w.buf1 = reinterpret_cast<float4*>(take(points * sizeof(float4)));
+    w.shift = reinterpret_cast<unsigned*>(take(3 * sizeof(unsigned) * G));
+    w.rounds = reinterpret_cast<int*>(take(sizeof(int) * G));
+    w.best = reinterpret_cast<unsigned long long*>(take(sizeof(unsigned long long) * G));
+    w.tail_bytes = off - 2 * align256(points * sizeof(float4));
+    w.rep = reinterpret_cast<unsigned*>(take(points * sizeof(unsigned)));
+    w.owner = reinterpret_cast<unsigned*>(take(points * sizeof(unsigned)));
+    w.big_bytes = 5 * sizeof(int) * G;
+    w.big_ids = reinterpret_cast<int*>(take(w.big_bytes));
+    w.len_of = w.big_ids + G; w.state_of = w.big_ids + 2 * G; w.dups_of = w.big_ids + 4 * G;
+    w.move_of = reinterpret_cast<unsigned*>(w.big_ids + 3 * G);
+    w.bytes = off;
+    return w;
+}
+
+// the process-wide switches as one call sees them (read once, at entry)
+struct Switches {
+    int fit_form, fit_spread, big_form;
+    float4* conv;                             // test hook: converged position of every point, [G,stride] (multi calls only)
+};
+
+// one time per device: the one-workgroup fits and the spread rounds may use their dynamic LDS; false = the device refuses it
+bool fit_kernels_allowed() {
+    static int attr_set[ffb6d::kMaxDevices + 1];
+    const int slot = ffb6d::device_slot();
+    if (ffb6d::cache_get(attr_set, slot)) return true;
+    auto allow = [](const void* kernel, size_t bytes) {
+        return hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(bytes)) == hipSuccess;
+    };
+    const bool ok = allow(reinterpret_cast<const void*>(&mean_shift_fit_kernel<1024, kCap>), fit_lds_bytes(kCap)) &&
+                    allow(reinterpret_cast<const void*>(&mean_shift_fit_kernel<512, kCapLight>), fit_lds_bytes(kCapLight)) &&
+                    allow(reinterpret_cast<const void*>(&mean_shift_fit_kernel<1024, kCap, true>), fit_lds_bytes(kCap)) &&
+                    allow(reinterpret_cast<const void*>(&mean_shift_fit_kernel<512, kCapLight, true>), fit_lds_bytes(kCapLight)) &&
+                    allow(reinterpret_cast<const void*>(&mean_shift_spread_round_kernel), 4 * sizeof(float) * kCap);
+    if (ok) ffb6d::cache_set(attr_set, slot, 1);
+    else (void)hipGetLastError();
+    return ok;
+}
+
+int cu_count() {
+    static int cached[ffb6d::kMaxDevices + 1];
+    const int slot = ffb6d::device_slot();
+    int cus = ffb6d::cache_get(cached, slot);
+    if (cus == 0) {
+        int dev = 0;
+        if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus < 1)
+            cus = 256;
+        ffb6d::cache_set(cached, slot, cus);
+    }
+    return cus;
+}
+
+// The parameters of mean_shift_fit_kernel by name (host only: the kernel takes them in this order) and its four instantiations
+// behind one launch.  A call fills the fields without an initialiser once; the launches set what differs between them.
+struct FitArgs {
+    const float4* sets; const int* counts; int sets_per_count; int64_t stride;
+    float k2, thresh, bandwidth; int max_iter;
+    float* centers; unsigned char* labels; int *n_inside, *iters, *rounds_ws, *n_large;
+    int m_lo = 0, count_large = 0;            // sets of up to m_lo points are not this launch's; count_large: it counts the sets above its cap
+    const float4 *pre0 = nullptr, *pre1 = nullptr;              // rounds 0 and 1 as the spread rounds made them, pre_move: their moves
+    const unsigned* pre_move = nullptr;
+    int G;
+    const float4* sets_odd = nullptr;         // with start_of: the launch continues fits begun chip-wide
+    const int* start_of = nullptr;
+    // max_clusters > 0 (ffb6d_mean_shift_multi_f32): the peeling tails; centers [G,K,3], labels = cluster u8 [G,stride], n_inside [G,K]
+    int max_clusters, min_inside; int* n_clusters; float4* conv_out;
     hipStream_t st;
-    unsigned G;
-    MultiArgs multi;
-    template <typename... A>
-    void operator()(bool light, A... a) const {
-        if (multi.K > 0) {
-            if (light) mean_shift_fit_kernel<512, kCapLight, true><<<G, 512, fit_lds_bytes(kCapLight), st>>>(a..., multi.K, multi.min_inside, multi.n_clusters, multi.conv);
-            else mean_shift_fit_kernel<1024, kCap, true><<<G, 1024, fit_lds_bytes(kCap), st>>>(a..., multi.K, multi.min_inside, multi.n_clusters, multi.conv);
-        } else {
-            if (light) mean_shift_fit_kernel<512, kCapLight><<<G, 512, fit_lds_bytes(kCapLight), st>>>(a..., 0, 0, static_cast<int*>(nullptr), static_cast<float4*>(nullptr));
-            else mean_shift_fit_kernel<1024, kCap><<<G, 1024, fit_lds_bytes(kCap), st>>>(a..., 0, 0, static_cast<int*>(nullptr), static_cast<float4*>(nullptr));
-        }
+
+    template <int kBT, int kSetCap, bool kMulti>
+    void launch_as() const {
+        mean_shift_fit_kernel<kBT, kSetCap, kMulti><<<static_cast<unsigned>(G), kBT, fit_lds_bytes(kSetCap), st>>>(
+            sets, counts, sets_per_count, stride, k2, thresh, bandwidth, max_iter, centers, labels, n_inside, iters, rounds_ws, n_large, m_lo,
+            count_large, pre0, pre1, pre_move, G, sets_odd, start_of, max_clusters, min_inside, n_clusters, conv_out);
+    }
+    void launch(bool light) const {
+        if (max_clusters > 0) light ? launch_as<512, kCapLight, true>() : launch_as<1024, kCap, true>();
+        else light ? launch_as<512, kCapLight, false>() : launch_as<1024, kCap, false>();
     }
 };
 
-int mean_shift_run(const float* sets, const int* counts, int sets_per_count, int G, int64_t set_stride,
-                   int64_t max_count, float bandwidth, int max_iter, int check_every, float* centers,
-                   unsigned char* labels,
-                   int* n_inside, int* iters, void* workspace, size_t workspace_bytes, ffb6d_stream_t stream, const MultiArgs multi) {
-    FFB6D_REQUIRE(G >= 0 && set_stride > 0 && sets_per_count > 0, "mean_shift: bad sizes G=%d stride=%lld", G,
-                  (long long)set_stride);
-    FFB6D_REQUIRE(bandwidth > 0.f && max_iter >= 0 && check_every >= 0, "mean_shift: bad bandwidth/max_iter");
-    FFB6D_REQUIRE(max_count >= 0 && max_count <= set_stride, "mean_shift: max_count %lld outside [0, set_stride]",
-                  (long long)max_count);
-    if (G == 0) return 0;
-    FFB6D_REQUIRE(sets && counts && centers, "mean_shift: null pointer");
-    const size_t need = ffb6d_mean_shift_workspace_bytes(G, set_stride);
-    if (!workspace || workspace_bytes < need)
-        return ffb6d::set_error(FFB6D_ERR_WORKSPACE, "mean_shift: workspace %zu < %zu bytes", workspace_bytes, need);
-    hipStream_t st = ffb6d::as_stream(stream);
-    char* w = static_cast<char*>(workspace);
-    const size_t buf_bytes = align256(static_cast<size_t>(G) * set_stride * sizeof(float4));
-    float4* buf0 = reinterpret_cast<float4*>(w);
-    float4* buf1 = reinterpret_cast<float4*>(w + buf_bytes);
-    char* tail = w + 2 * buf_bytes;
-    unsigned* shift = reinterpret_cast<unsigned*>(tail);
-    int* rounds = reinterpret_cast<int*>(tail + align256(3 * sizeof(unsigned) * G));
-    unsigned long long* best =
-        reinterpret_cast<unsigned long long*>(tail + align256(3 * sizeof(unsigned) * G) + align256(sizeof(int) * G));
-    const size_t tail_bytes = align256(3 * sizeof(unsigned) * G) + align256(sizeof(int) * G) + align256(sizeof(unsigned long long) * G);
-    const size_t map_bytes = align256(static_cast<size_t>(G) * set_stride * sizeof(unsigned));
-    unsigned* rep = reinterpret_cast<unsigned*>(tail + tail_bytes);
-    unsigned* owner = reinterpret_cast<unsigned*>(tail + tail_bytes + map_bytes);
-    int* big_ids = reinterpret_cast<int*>(tail + tail_bytes + 2 * map_bytes);
-    int *len_of = big_ids + G, *state_of = big_ids + 2 * G, *dups_of = big_ids + 4 * G;
-    unsigned* move_of = reinterpret_cast<unsigned*>(big_ids + 3 * G);
-    FFB6D_HIP_TRY(hipMemsetAsync(tail, 0, tail_bytes, st));
+// what the phases of one call share: its arguments as the first fit launch takes them, the switches, the workspace
+struct MeanShiftCall {
+    FitArgs fit;
+    int check_every, min_cnt;                 // sets of more than min_cnt points are fitted round by round (-1: every set)
+    Switches sw;
+    MeanShiftWorkspace ws;
+};
 
-    const double inv_bw2 = 1.0 / (static_cast<double>(bandwidth) * static_cast<double>(bandwidth));
-    const float k2 = static_cast<float>(-0.5 * 1.4426950408889634 * inv_bw2);
-    const float thresh = static_cast<float>(static_cast<double>(bandwidth) * 1e-3);   // stop_thresh (:30)
-
-    // Sets of up to kCap points: the whole fit in one workgroup each, one launch for all of them (duplicate merging, no polling).
-    // `best` doubles as the counter of the sets that are larger (one int at its start; cleared above, cleared again before the
-    // round-by-round path uses the array).
-    int* n_large = reinterpret_cast<int*>(best);
-    bool fit_ok = true;                                        // a device that refuses the dynamic LDS: every set takes the round-by-round path
-    {
-        static int attr_set[ffb6d::kMaxDevices + 1];
-        const int slot = ffb6d::device_slot();
-        if (!ffb6d::cache_get(attr_set, slot)) {
-            fit_ok = hipFuncSetAttribute(reinterpret_cast<const void*>(&mean_shift_fit_kernel<1024, kCap>),
-                                         hipFuncAttributeMaxDynamicSharedMemorySize, fit_lds_bytes(kCap)) == hipSuccess &&
-                     hipFuncSetAttribute(reinterpret_cast<const void*>(&mean_shift_fit_kernel<512, kCapLight>),
-                                         hipFuncAttributeMaxDynamicSharedMemorySize, fit_lds_bytes(kCapLight)) == hipSuccess &&
-                     hipFuncSetAttribute(reinterpret_cast<const void*>(&mean_shift_fit_kernel<1024, kCap, true>),
-                                         hipFuncAttributeMaxDynamicSharedMemorySize, fit_lds_bytes(kCap)) == hipSuccess &&
-                     hipFuncSetAttribute(reinterpret_cast<const void*>(&mean_shift_fit_kernel<512, kCapLight, true>),
-                                         hipFuncAttributeMaxDynamicSharedMemorySize, fit_lds_bytes(kCapLight)) == hipSuccess &&
-                     hipFuncSetAttribute(reinterpret_cast<const void*>(&mean_shift_spread_round_kernel),
-                                         hipFuncAttributeMaxDynamicSharedMemorySize, 4 * sizeof(float) * kCap) == hipSuccess;
-            if (fit_ok) ffb6d::cache_set(attr_set, slot, 1);
-            else (void)hipGetLastError();
-        }
-    }
-    const int min_cnt = fit_ok ? kCap : -1;                    // sets above it are fitted round by round
-    const FitLaunch fit{st, static_cast<unsigned>(G), multi};
-    if (fit_ok) {
-        const float4* s4 = reinterpret_cast<const float4*>(sets);
-        // the first two rounds of the sets of kSpreadMin .. kCap points, 128 points per workgroup
-        const float4 *pre0 = nullptr, *pre1 = nullptr;
-        bool spread = g_fit_spread == 2;
-        if (g_fit_spread == 1) {
-            static int cu_count[ffb6d::kMaxDevices + 1];
-            const int slot = ffb6d::device_slot();
-            int cus = ffb6d::cache_get(cu_count, slot);
-            if (cus == 0) {
-                int dev = 0;
-                if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus < 1)
-                    cus = 256;
-                ffb6d::cache_set(cu_count, slot, cus);
-            }
-            spread = 2 * G <= cus;
-        }
-        if (spread && set_stride >= kSpreadMin) {
-            const int cap = static_cast<int>(std::min<int64_t>((set_stride + 7) & ~int64_t(7), kCap));
-            const dim3 sgrid(static_cast<unsigned>(ceil_div(cap, kSpreadBT / 4)), static_cast<unsigned>(G));
-            const size_t slds = 4 * sizeof(float) * static_cast<size_t>(cap);
-            mean_shift_spread_round_kernel<<<sgrid, kSpreadBT, slds, st>>>(s4, counts, sets_per_count, set_stride, cap, k2, buf0, shift);
-            FFB6D_LAUNCH_CHECK();
-            mean_shift_spread_round_kernel<<<sgrid, kSpreadBT, slds, st>>>(buf0, counts, sets_per_count, set_stride, cap, k2, buf1, shift + G);
-            FFB6D_LAUNCH_CHECK();
-            pre0 = buf0;
-            pre1 = buf1;
-        }
-        if (g_fit_form == 1) {
-            fit(true, s4, counts, sets_per_count, set_stride, k2, thresh, bandwidth, max_iter, centers, labels, n_inside, iters, rounds, n_large, 0, 0,
-                pre0, pre1, shift, G, nullptr, nullptr);
-            FFB6D_LAUNCH_CHECK();
-            if (set_stride > kCapLight) {
-                fit(false, s4, counts, sets_per_count, set_stride, k2, thresh, bandwidth, max_iter, centers, labels, n_inside, iters, rounds, n_large,
-                    kCapLight, 1, pre0, pre1, shift, G, nullptr, nullptr);
-                FFB6D_LAUNCH_CHECK();
-            }
-        } else {
-            fit(false, s4, counts, sets_per_count, set_stride, k2, thresh, bandwidth, max_iter, centers, labels, n_inside, iters, rounds, n_large, 0, 1,
-                pre0, pre1, shift, G, nullptr, nullptr);
-            FFB6D_LAUNCH_CHECK();
-        }
-    }
-    if (fit_ok) {
-        if (set_stride <= kCap) return 0;                      // no set can be larger
-        int large = 0;                                         // one read-back per call (the old path polled every `check_every` rounds)
-        FFB6D_HIP_TRY(hipMemcpyAsync(&large, n_large, sizeof(int), hipMemcpyDeviceToHost, st));
-        FFB6D_HIP_TRY(hipStreamSynchronize(st));
-        if (large == 0) return 0;
-    }
-
-    // blocks beyond a set's count exit at once: the largest count sizes the grids
-    std::vector<int> host_counts(static_cast<size_t>(ceil_div(G, sets_per_count)));       // (the kernels index counts[g / sets_per_count], g < G)
-    FFB6D_HIP_TRY(hipMemcpyAsync(host_counts.data(), counts, sizeof(int) * host_counts.size(), hipMemcpyDeviceToHost, st));
-    FFB6D_HIP_TRY(hipStreamSynchronize(st));
-
-    // ---- sets of more than kCap points: chip-wide rounds with duplicate merging, then the one-workgroup fit (round 6) ----
-    const int* handed = nullptr;
-    if (fit_ok && g_big_form) {
-        std::vector<int> ids;
-        int64_t span = 1;
-        for (int g = 0; g < G; ++g) {
-            const int c = host_counts[g / sets_per_count];
-            if (c > kCap) { ids.push_back(g); span = std::max<int64_t>(span, std::min<int64_t>(c, set_stride)); }
-        }
-        const unsigned n_big = static_cast<unsigned>(ids.size());
-        if (n_big == 0) return 0;                              // (every set was fitted above)
-        FFB6D_HIP_TRY(hipMemsetAsync(big_ids, 0, 5 * sizeof(int) * G, st));
-        FFB6D_HIP_TRY(hipMemcpyAsync(big_ids, ids.data(), sizeof(int) * n_big, hipMemcpyHostToDevice, st));
-        big_init_kernel<<<dim3(static_cast<unsigned>(ceil_div(span, kBlock)), n_big), kBlock, 0, st>>>(reinterpret_cast<const float4*>(sets), counts, sets_per_count, set_stride,
-                                                                                                     big_ids, buf0, owner, len_of);
+// Sets of up to kCap points: the whole fit in one workgroup each, one launch for all of them (duplicate merging, no polling).
+// The launches count the larger sets in ws.n_large().
+int run_small_fits(const MeanShiftCall& c) {
+    FitArgs f = c.fit;
+    // the first two rounds of the sets of kSpreadMin .. kCap points, 128 points per workgroup
+    const bool spread = c.sw.fit_spread == 2 || (c.sw.fit_spread == 1 && 2 * f.G <= cu_count());
+    if (spread && f.stride >= kSpreadMin) {
+        const int cap = static_cast<int>(std::min<int64_t>((f.stride + 7) & ~int64_t(7), kCap));
+        const dim3 sgrid(static_cast<unsigned>(ceil_div(cap, kSpreadBT / 4)), static_cast<unsigned>(f.G));
+        const size_t slds = 4 * sizeof(float) * static_cast<size_t>(cap);
+        mean_shift_spread_round_kernel<<<sgrid, kSpreadBT, slds, f.st>>>(f.sets, f.counts, f.sets_per_count, f.stride, cap, f.k2, c.ws.buf0, c.ws.shift);
         FFB6D_LAUNCH_CHECK();
-        std::vector<int> host_state(2 * static_cast<size_t>(G));           // len_of | state_of: adjacent in the workspace, one copy
-        bool polled = false;
-        for (int t = 0; t <= max_iter && t < kBigRounds; ++t) {
-            big_round_kernel<<<dim3(static_cast<unsigned>(ceil_div(span, kPointsPerBlock)), n_big), kBlock, 0, st>>>(
-                buf0, buf1, set_stride, big_ids, k2, t, len_of, state_of, rep, move_of, dups_of);
-            FFB6D_LAUNCH_CHECK();
-            big_compact_kernel<<<n_big, kCompactBT, 0, st>>>(buf0, buf1, set_stride, big_ids, counts, sets_per_count, thresh, t, len_of, state_of,
-                                                            move_of, dups_of, rep, owner);
-            FFB6D_LAUNCH_CHECK();
-            polled = false;
-            if (t >= 2) {                                      // (nothing merges in the first rounds)
-                FFB6D_HIP_TRY(hipMemcpyAsync(host_state.data(), len_of, 2 * sizeof(int) * G, hipMemcpyDeviceToHost, st));
-                FFB6D_HIP_TRY(hipStreamSynchronize(st));
-                polled = true;
-                bool ready = true;
-                span = 1;
-                for (int g : ids) {
-                    const bool conv = host_state[G + g] >> 29;          // converged or given up
-                    ready = ready && (conv || host_state[g] <= kCap);
-                    if (!conv) span = std::max<int64_t>(span, host_state[g]);
-                }
-                if (ready) break;
-            }
-        }
-        if (!polled) {
-            FFB6D_HIP_TRY(hipMemcpyAsync(host_state.data(), len_of, 2 * sizeof(int) * G, hipMemcpyDeviceToHost, st));
-            FFB6D_HIP_TRY(hipStreamSynchronize(st));
-        }
-        // the fits continue from the lists (sets whose list is still longer: untouched, counted below)
-        unsigned char* fit_labels = labels ? reinterpret_cast<unsigned char*>(rep) : nullptr;       // (the representatives are dead)
-        if (g_fit_form == 1) {
-            fit(true, buf0, len_of, 1, set_stride, k2, thresh, bandwidth, max_iter, centers, fit_labels, n_inside, iters, rounds, n_large, 0, 0,
-                nullptr, nullptr, nullptr, G, buf1, state_of);
-            FFB6D_LAUNCH_CHECK();
-        }
-        fit(false, buf0, len_of, 1, set_stride, k2, thresh, bandwidth, max_iter, centers, fit_labels, n_inside, iters, rounds, n_large,
-            g_fit_form == 1 ? kCapLight : 0, 0, nullptr, nullptr, nullptr, G, buf1, state_of);
+        mean_shift_spread_round_kernel<<<sgrid, kSpreadBT, slds, f.st>>>(c.ws.buf0, f.counts, f.sets_per_count, f.stride, cap, f.k2, c.ws.buf1, c.ws.shift + f.G);
         FFB6D_LAUNCH_CHECK();
-        if (labels) {
-            big_labels_kernel<<<dim3(static_cast<unsigned>(ceil_div(set_stride, kBlock)), n_big), kBlock, 0, st>>>(
-                big_ids, counts, sets_per_count, set_stride, len_of, kCap, fit_labels, owner, labels);
-            FFB6D_LAUNCH_CHECK();
-        }
-        if (multi.conv) {
-            big_converged_kernel<<<dim3(static_cast<unsigned>(ceil_div(set_stride, kBlock)), n_big), kBlock, 0, st>>>(
-                big_ids, counts, sets_per_count, set_stride, len_of, kCap, state_of, buf0, buf1, owner, reinterpret_cast<const float4*>(sets),
-                multi.conv);
-            FFB6D_LAUNCH_CHECK();
-        }
-        bool left = false;
-        for (int g : ids) left = left || host_state[g] > kCap;
-        if (!left) return 0;
-        handed = len_of;                                       // the round-by-round kernels skip the sets with lists of <= kCap positions
+        f.pre0 = c.ws.buf0;
+        f.pre1 = c.ws.buf1;
     }
+    f.pre_move = c.ws.shift;
+    if (c.sw.fit_form == 1) {                                  // the light form, then the sets above its cap on the large one
+        f.launch(true);
+        FFB6D_LAUNCH_CHECK();
+        if (f.stride <= kCapLight) return 0;
+        f.m_lo = kCapLight;
+    }
+    f.count_large = 1;
+    f.launch(false);
+    FFB6D_LAUNCH_CHECK();
+    return 0;
+}
 
-    // ---- what is left: one launch per round for all of those sets (round-1 path) ----
-    FFB6D_HIP_TRY(hipMemsetAsync(best, 0, sizeof(unsigned long long) * G, st));
-    FFB6D_HIP_TRY(hipMemsetAsync(shift, 0, 3 * sizeof(unsigned) * G, st));     // (the spread rounds of the fits used two of the slots)
-    FFB6D_HIP_TRY(hipMemcpyAsync(buf0, sets, static_cast<size_t>(G) * set_stride * sizeof(float4),
-                                 hipMemcpyDeviceToDevice, st));
+int read_big_state(const MeanShiftCall& c, std::vector<int>& host_state) {       // len_of | state_of in one copy
+    FFB6D_HIP_TRY(hipMemcpyAsync(host_state.data(), c.ws.len_of, 2 * sizeof(int) * c.fit.G, hipMemcpyDeviceToHost, c.fit.st));
+    FFB6D_HIP_TRY(hipStreamSynchronize(c.fit.st));
+    return 0;
+}
+
+// Sets of more than kCap points: chip-wide rounds with duplicate merging, then the one-workgroup fit continues from the lists.
+// *handed: NULL when no set is left for the round-by-round path, else the list lengths (its kernels skip the sets with lists of
+// <= kCap positions).
+int run_big_sets(const MeanShiftCall& c, const std::vector<int>& host_counts, const int** handed) {
+    const FitArgs& a = c.fit;
+    const MeanShiftWorkspace& w = c.ws;
+    const int G = a.G;
+    *handed = nullptr;
+    std::vector<int> ids;
     int64_t span = 1;
-    for (int c : host_counts) span = std::max<int64_t>(span, std::min<int64_t>(c, set_stride));
-    (void)max_count;
+    for (int g = 0; g < G; ++g) {
+        const int n = host_counts[g / a.sets_per_count];
+        if (n > kCap) { ids.push_back(g); span = std::max<int64_t>(span, std::min<int64_t>(n, a.stride)); }
+    }
+    const unsigned n_big = static_cast<unsigned>(ids.size());
+    if (n_big == 0) return 0;                                  // (every set was fitted before)
+    FFB6D_HIP_TRY(hipMemsetAsync(w.big_ids, 0, w.big_bytes, a.st));
+    FFB6D_HIP_TRY(hipMemcpyAsync(w.big_ids, ids.data(), sizeof(int) * n_big, hipMemcpyHostToDevice, a.st));
+    big_init_kernel<<<dim3(static_cast<unsigned>(ceil_div(span, kBlock)), n_big), kBlock, 0, a.st>>>(a.sets, a.counts, a.sets_per_count, a.stride, w.big_ids,
+                                                                                                   w.buf0, w.owner, w.len_of);
+    FFB6D_LAUNCH_CHECK();
+    std::vector<int> host_state(2 * static_cast<size_t>(G));
+    bool polled = false;
+    for (int t = 0; t <= a.max_iter && t < kBigRounds; ++t) {
+        big_round_kernel<<<dim3(static_cast<unsigned>(ceil_div(span, kPointsPerBlock)), n_big), kBlock, 0, a.st>>>(
+            w.buf0, w.buf1, a.stride, w.big_ids, a.k2, t, w.len_of, w.state_of, w.rep, w.move_of, w.dups_of);
+        FFB6D_LAUNCH_CHECK();
+        big_compact_kernel<<<n_big, kCompactBT, 0, a.st>>>(w.buf0, w.buf1, a.stride, w.big_ids, a.counts, a.sets_per_count, a.thresh, t, w.len_of, w.state_of,
+                                                          w.move_of, w.dups_of, w.rep, w.owner);
+        FFB6D_LAUNCH_CHECK();
+        polled = t >= 2;                                       // (nothing merges in the first rounds)
+        if (!polled) continue;
+        if (const int rc = read_big_state(c, host_state)) return rc;
+        bool ready = true;
+        span = 1;
+        for (int g : ids) {
+            const bool conv = host_state[G + g] >> 29;         // converged or given up
+            ready = ready && (conv || host_state[g] <= kCap);
+            if (!conv) span = std::max<int64_t>(span, host_state[g]);
+        }
+        if (ready) break;
+    }
+    if (!polled)
+        if (const int rc = read_big_state(c, host_state)) return rc;
+    // the fits continue from the lists (sets whose list is still longer: untouched, counted below)
+    FitArgs f = a;
+    f.sets = w.buf0; f.counts = w.len_of; f.sets_per_count = 1; f.labels = a.labels ? w.fit_labels() : nullptr; f.sets_odd = w.buf1; f.start_of = w.state_of;
+    if (c.sw.fit_form == 1) {
+        f.launch(true);
+        FFB6D_LAUNCH_CHECK();
+        f.m_lo = kCapLight;
+    }
+    f.launch(false);
+    FFB6D_LAUNCH_CHECK();
+    const dim3 pgrid(static_cast<unsigned>(ceil_div(a.stride, kBlock)), n_big);
+    if (a.labels) {
+        big_labels_kernel<<<pgrid, kBlock, 0, a.st>>>(w.big_ids, a.counts, a.sets_per_count, a.stride, w.len_of, kCap, f.labels, w.owner, a.labels);
+        FFB6D_LAUNCH_CHECK();
+    }
+    if (c.sw.conv) {
+        big_converged_kernel<<<pgrid, kBlock, 0, a.st>>>(w.big_ids, a.counts, a.sets_per_count, a.stride, w.len_of, kCap, w.state_of, w.buf0, w.buf1, w.owner,
+                                                        a.sets, c.sw.conv);
+        FFB6D_LAUNCH_CHECK();
+    }
+    for (int g : ids)
+        if (host_state[g] > kCap) *handed = w.len_of;
+    return 0;
+}
+
+// What is left: one launch per round for all of those sets, polled every `check_every` rounds, then the peel or the largest ball.
+int run_round_by_round(const MeanShiftCall& c, const std::vector<int>& host_counts, const int* handed) {
+    const FitArgs& a = c.fit;
+    const MeanShiftWorkspace& w = c.ws;
+    const int G = a.G;
+    FFB6D_HIP_TRY(hipMemsetAsync(w.best, 0, sizeof(unsigned long long) * G, a.st));
+    FFB6D_HIP_TRY(hipMemsetAsync(w.shift, 0, 3 * sizeof(unsigned) * G, a.st));     // (the spread rounds of the fits used two of the slots)
+    FFB6D_HIP_TRY(hipMemcpyAsync(w.buf0, a.sets, static_cast<size_t>(G) * a.stride * sizeof(float4), hipMemcpyDeviceToDevice, a.st));
+    int64_t span = 1;                                          // blocks beyond a set's count exit at once: the largest count sizes the grids
+    for (int n : host_counts) span = std::max<int64_t>(span, std::min<int64_t>(n, a.stride));
     const dim3 grid(static_cast<unsigned>(ceil_div(span, kPointsPerBlock)), static_cast<unsigned>(G));
     std::vector<float> host_shift;
     std::vector<int> host_handed;
-    if (check_every > 0) host_shift.resize(G);
+    if (c.check_every > 0) host_shift.resize(G);
     if (handed) {
         host_handed.resize(G);
-        FFB6D_HIP_TRY(hipMemcpyAsync(host_handed.data(), handed, sizeof(int) * G, hipMemcpyDeviceToHost, st));
-        FFB6D_HIP_TRY(hipStreamSynchronize(st));
+        FFB6D_HIP_TRY(hipMemcpyAsync(host_handed.data(), handed, sizeof(int) * G, hipMemcpyDeviceToHost, a.st));
+        FFB6D_HIP_TRY(hipStreamSynchronize(a.st));
     }
-    for (int t = 0; t <= max_iter; ++t) {       // `it > max_iter` stops after max_iter+1 rounds (:47)
-        mean_shift_round_kernel<<<grid, kBlock, 0, st>>>(buf0, buf1, counts, sets_per_count, set_stride, k2, thresh,
-                                                         shift, rounds, t, G, min_cnt, handed);
+    for (int t = 0; t <= a.max_iter; ++t) {       // `it > max_iter` stops after max_iter+1 rounds (:47)
+        mean_shift_round_kernel<<<grid, kBlock, 0, a.st>>>(w.buf0, w.buf1, a.counts, a.sets_per_count, a.stride, a.k2, a.thresh, w.shift, w.rounds, t, G,
+                                                          c.min_cnt, handed);
         FFB6D_LAUNCH_CHECK();
-        if (check_every > 0 && (t + 1) % check_every == 0 && t < max_iter) {
-            FFB6D_HIP_TRY(hipMemcpyAsync(host_shift.data(), shift + (t % 3) * G, sizeof(float) * G,
-                                         hipMemcpyDeviceToHost, st));
-            FFB6D_HIP_TRY(hipStreamSynchronize(st));
+        if (c.check_every > 0 && (t + 1) % c.check_every == 0 && t < a.max_iter) {
+            FFB6D_HIP_TRY(hipMemcpyAsync(host_shift.data(), w.shift + (t % 3) * G, sizeof(float) * G, hipMemcpyDeviceToHost, a.st));
+            FFB6D_HIP_TRY(hipStreamSynchronize(a.st));
             bool all_done = true;
             for (int g = 0; g < G && all_done; ++g)
-                all_done = host_counts[g / sets_per_count] <= min_cnt || (handed && host_handed[g] <= min_cnt) || host_shift[g] < thresh;
+                all_done = host_counts[g / a.sets_per_count] <= c.min_cnt || (handed && host_handed[g] <= c.min_cnt) || host_shift[g] < a.thresh;
             if (all_done) break;
         }
     }
-    if (multi.K > 0) {
-        peel_points_kernel<<<static_cast<unsigned>(G), kPeelBT, 0, st>>>(buf0, buf1, counts, sets_per_count, set_stride, bandwidth, rounds, multi.K,
-                                                                          multi.min_inside, centers, n_inside, multi.n_clusters, labels, iters, min_cnt,
-                                                                          handed, reinterpret_cast<int*>(rep), owner, multi.conv);
+    if (a.max_clusters > 0) {
+        peel_points_kernel<<<static_cast<unsigned>(G), kPeelBT, 0, a.st>>>(w.buf0, w.buf1, a.counts, a.sets_per_count, a.stride, a.bandwidth, w.rounds,
+                                                                            a.max_clusters, a.min_inside, a.centers, a.n_inside, a.n_clusters, a.labels,
+                                                                            a.iters, c.min_cnt, handed, w.peel_sizes(), w.peel_removed(), c.sw.conv);
         FFB6D_LAUNCH_CHECK();
         return 0;
     }
-    ball_count_kernel<<<grid, kBlock, 0, st>>>(buf0, buf1, counts, sets_per_count, set_stride, bandwidth, rounds, best, min_cnt, handed);
+    ball_count_kernel<<<grid, kBlock, 0, a.st>>>(w.buf0, w.buf1, a.counts, a.sets_per_count, a.stride, a.bandwidth, w.rounds, w.best, c.min_cnt, handed);
     FFB6D_LAUNCH_CHECK();
-    const dim3 lgrid(static_cast<unsigned>(labels ? ceil_div(set_stride, kBlock) : 1), static_cast<unsigned>(G));
-    ball_labels_kernel<<<lgrid, kBlock, 0, st>>>(buf0, buf1, counts, sets_per_count, set_stride, bandwidth, rounds, best,
-                                                 centers, labels, n_inside, iters, min_cnt, handed);
+    const dim3 lgrid(static_cast<unsigned>(a.labels ? ceil_div(a.stride, kBlock) : 1), static_cast<unsigned>(G));
+    ball_labels_kernel<<<lgrid, kBlock, 0, a.st>>>(w.buf0, w.buf1, a.counts, a.sets_per_count, a.stride, a.bandwidth, w.rounds, w.best, a.centers, a.labels,
+                                                 a.n_inside, a.iters, c.min_cnt, handed);
     FFB6D_LAUNCH_CHECK();
     return 0;
+}
+
+// check the arguments, lay out and clear the workspace, the small fits, the big sets, the rest round by round (max_clusters = 0: the single fit)
+int mean_shift_run(const float* sets, const int* counts, int sets_per_count, int G, int64_t set_stride, int64_t max_count, float bandwidth,
+                   int max_iter, int check_every, float* centers, unsigned char* labels, int* n_inside, int* iters, void* workspace,
+                   size_t workspace_bytes, ffb6d_stream_t stream, int max_clusters, int min_inside, int* n_clusters) {
+    FFB6D_REQUIRE(G >= 0 && set_stride > 0 && sets_per_count > 0, "mean_shift: bad sizes G=%d stride=%lld", G, (long long)set_stride);
+    FFB6D_REQUIRE(bandwidth > 0.f && max_iter >= 0 && check_every >= 0, "mean_shift: bad bandwidth/max_iter");
+    FFB6D_REQUIRE(max_count >= 0 && max_count <= set_stride, "mean_shift: max_count %lld outside [0, set_stride]", (long long)max_count);
+    if (G == 0) return 0;
+    FFB6D_REQUIRE(sets && counts && centers, "mean_shift: null pointer");
+    MeanShiftCall c;
+    c.ws = mean_shift_layout(workspace, G, set_stride);
+    if (!workspace || workspace_bytes < c.ws.bytes)
+        return ffb6d::set_error(FFB6D_ERR_WORKSPACE, "mean_shift: workspace %zu < %zu bytes", workspace_bytes, c.ws.bytes);
+    c.sw = Switches{g_fit_form, g_fit_spread, g_big_form, max_clusters > 0 ? g_converged_out : nullptr};
+    c.check_every = check_every;
+    FitArgs& f = c.fit;
+    f.sets = reinterpret_cast<const float4*>(sets); f.counts = counts; f.sets_per_count = sets_per_count; f.stride = set_stride; f.G = G;
+    f.bandwidth = bandwidth; f.max_iter = max_iter; f.centers = centers; f.labels = labels; f.n_inside = n_inside; f.iters = iters;
+    f.rounds_ws = c.ws.rounds; f.n_large = c.ws.n_large(); f.st = ffb6d::as_stream(stream);
+    f.max_clusters = max_clusters; f.min_inside = min_inside; f.n_clusters = n_clusters; f.conv_out = c.sw.conv;
+    const double inv_bw2 = 1.0 / (static_cast<double>(bandwidth) * static_cast<double>(bandwidth));
+    f.k2 = static_cast<float>(-0.5 * 1.4426950408889634 * inv_bw2);
+    f.thresh = static_cast<float>(static_cast<double>(bandwidth) * 1e-3);   // stop_thresh (:30)
+    FFB6D_HIP_TRY(hipMemsetAsync(c.ws.shift, 0, c.ws.tail_bytes, f.st));
+
+    const bool fit_ok = fit_kernels_allowed();                 // a device that refuses the dynamic LDS: every set takes the round-by-round path
+    c.min_cnt = fit_ok ? kCap : -1;
+    if (fit_ok) {
+        if (const int rc = run_small_fits(c)) return rc;
+        if (set_stride <= kCap) return 0;                      // no set can be larger
+        int large = 0;                                         // one read-back per call
+        FFB6D_HIP_TRY(hipMemcpyAsync(&large, c.ws.n_large(), sizeof(int), hipMemcpyDeviceToHost, f.st));
+        FFB6D_HIP_TRY(hipStreamSynchronize(f.st));
+        if (large == 0) return 0;
+    }
+    std::vector<int> host_counts(static_cast<size_t>(ceil_div(G, sets_per_count)));       // (the kernels index counts[g / sets_per_count], g < G)
+    FFB6D_HIP_TRY(hipMemcpyAsync(host_counts.data(), counts, sizeof(int) * host_counts.size(), hipMemcpyDeviceToHost, f.st));
+    FFB6D_HIP_TRY(hipStreamSynchronize(f.st));
+    const int* handed = nullptr;
+    if (fit_ok && c.sw.big_form) {
+        if (const int rc = run_big_sets(c, host_counts, &handed)) return rc;
+        if (!handed) return 0;                                 // every set is done
+    }
+    return run_round_by_round(c, host_counts, handed);
 }
 
 }  // namespace
 
 extern "C" {
 
+size_t ffb6d_mean_shift_workspace_bytes(int G, int64_t set_stride) {
+    if (G <= 0 || set_stride <= 0) return 0;
+    return mean_shift_layout(nullptr, G, set_stride).bytes;
+}
+
 int ffb6d_mean_shift_f32(const float* sets, const int* counts, int sets_per_count, int G, int64_t set_stride,
-                         int64_t max_count, float bandwidth, int max_iter, int check_every, float* centers,
-                         unsigned char* labels,
+                         int64_t max_count, float bandwidth, int max_iter, int check_every, float* centers, unsigned char* labels,
                          int* n_inside, int* iters, void* workspace, size_t workspace_bytes, ffb6d_stream_t stream) {
     return mean_shift_run(sets, counts, sets_per_count, G, set_stride, max_count, bandwidth, max_iter, check_every, centers, labels,
-                          n_inside, iters, workspace, workspace_bytes, stream, MultiArgs{});
+                          n_inside, iters, workspace, workspace_bytes, stream, 0, 0, nullptr);
 }
 
 void ffb6d_pose_set_converged_out(float* out) { g_converged_out = reinterpret_cast<float4*>(out); }
@@ -1403,13 +1449,8 @@ int ffb6d_mean_shift_multi_f32(const float* sets, const int* counts, int sets_pe
     FFB6D_REQUIRE(max_clusters >= 1 && max_clusters <= 255, "mean_shift_multi: max_clusters %d outside [1, 255] (ids are u8)", max_clusters);
     FFB6D_REQUIRE(min_inside >= 1, "mean_shift_multi: min_inside %d < 1", min_inside);
     FFB6D_REQUIRE(G <= 0 || (cluster && n_inside && n_clusters), "mean_shift_multi: null pointer");
-    MultiArgs multi;
-    multi.K = max_clusters;
-    multi.min_inside = min_inside;
-    multi.n_clusters = n_clusters;
-    multi.conv = g_converged_out;
     return mean_shift_run(sets, counts, sets_per_count, G, set_stride, max_count, bandwidth, max_iter, check_every, centers, cluster,
-                          n_inside, iters, workspace, workspace_bytes, stream, multi);
+                          n_inside, iters, workspace, workspace_bytes, stream, max_clusters, min_inside, n_clusters);
 }
 
 int ffb6d_set_clusters_to_points(const float* sets, const unsigned char* cluster, const int* counts, const int* frame_of,

@@ -6,7 +6,7 @@
     stage B  FFB6D.forward with the index pyramid built inside (22 exact-KNN searches per frame)             (ffb6d_amd.forward_pm)
     stage C  argmax of the segmentation, mean-shift voting per object / keypoint, least-squares fit         (ffb6d_amd.pose)
 
-`run(batches, overlap=False)` runs A, B, C of a batch one after the other.  `overlap=True` is the pipelined schedule: stage A of
+`run(batches, overlap=False)` runs A, B, C of a batch one after the other.  `overlap=True` (the default) is the pipelined schedule: stage A of
 batch i + 1 (a side stream) and stage C of batch i (another side stream; its host-side polling and read-backs too) run under stage B
 of batch i + 1 -- the stages of ONE batch still follow each other through events, so every batch's results are the bits the serial
 schedule produces (tests/test_pipeline_gpu.py).  No collective, no host geometry; the only read-backs are the poses.

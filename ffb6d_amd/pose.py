@@ -46,9 +46,8 @@ def _mask_bits(mask):
     raise TypeError(f"mask must be int32 or int64, got {mask.dtype}")
 
 
-def vote_sets(pcld, offsets, mask, frame_of, class_of, keep=None):
-    """Votes `pcld - offsets` of the points with mask == class, per (frame, class) pair.
-    pcld [B,N,3], offsets [B,S,N,3], mask [B,N] -> sets f32 [P*S, N, 4], counts i32 [P]."""
+def _vote_sets(pcld, offsets, mask, frame_of, class_of, keep=None, inst=None, inst_of=None):
+    """vote_sets (inst_of is None) and vote_sets_inst around their entry points"""
     _need_gpu(pcld, offsets, mask)
     B, N, _ = pcld.shape
     S = offsets.shape[1]
@@ -56,21 +55,29 @@ def vote_sets(pcld, offsets, mask, frame_of, class_of, keep=None):
     pcld, offsets, mask = pcld.contiguous().float(), offsets.contiguous().float(), mask.contiguous()
     sets = torch.empty((P * S, N, 4), dtype=torch.float32, device=pcld.device)
     counts = torch.zeros((P,), dtype=torch.int32, device=pcld.device)
+    head = (pcld.data_ptr(), offsets.data_ptr(), mask.data_ptr(), _mask_bits(mask))
+    tail = (P, B, S, N, N, sets.data_ptr(), counts.data_ptr(), _stream(pcld))
+    if inst_of is None:
+        name, rows = "ffb6d_vote_sets_f32", (keep.data_ptr() if keep is not None else None, frame_of.data_ptr(), class_of.data_ptr())
+    else:
+        name, rows = "ffb6d_vote_sets_inst_f32", (inst.data_ptr(), frame_of.data_ptr(), class_of.data_ptr(), inst_of.data_ptr())
     with torch.cuda.device(pcld.device), _lib.traced("vote_sets", 4 * (3 * B * N * (S + 1)) + 16 * P * S * N, (P, S, N)):
-        rc = _lib.load().ffb6d_vote_sets_f32(
-            pcld.data_ptr(), offsets.data_ptr(), mask.data_ptr(), _mask_bits(mask),
-            keep.data_ptr() if keep is not None else None, frame_of.data_ptr(), class_of.data_ptr(),
-            P, B, S, N, N, sets.data_ptr(), counts.data_ptr(), _stream(pcld))
-    _lib.check(rc, "ffb6d_vote_sets_f32")
+        rc = getattr(_lib.load(), name)(*head, *rows, *tail)
+    _lib.check(rc, name)
     return sets, counts
+
+
+def vote_sets(pcld, offsets, mask, frame_of, class_of, keep=None):
+    """Votes `pcld - offsets` of the points with mask == class, per (frame, class) pair.
+    pcld [B,N,3], offsets [B,S,N,3], mask [B,N] -> sets f32 [P*S, N, 4], counts i32 [P]."""
+    return _vote_sets(pcld, offsets, mask, frame_of, class_of, keep=keep)
 
 
 def mean_shift(sets, counts, bandwidth, max_iter=300, sets_per_count=1, want_labels=True, check_every=CHECK_EVERY,
                max_count=None):
     """MeanShiftTorch.fit for every set: sets f32 [G,M,4], counts i32 [G/sets_per_count] ->
     centers f32 [G,3], labels bool [G,M] (or None), n_inside i32 [G], rounds i32 [G].
-    max_count: bound on the counts (sizes the grids); None = read it back from `counts` when the
-    call polls the device anyway (check_every > 0), else unknown."""
+    max_count: accepted and ignored (the library sizes its grids itself; None = 0)."""
     _need_gpu(sets, counts)
     G, M, _ = sets.shape
     dev = sets.device
@@ -79,13 +86,11 @@ def mean_shift(sets, counts, bandwidth, max_iter=300, sets_per_count=1, want_lab
     n_inside = torch.empty((G,), dtype=torch.int32, device=dev)
     rounds = torch.empty((G,), dtype=torch.int32, device=dev)
     lib = _lib.load()
-    if max_count is None:
-        max_count = 0            # (round 5: the library sizes its grids itself; no read-back of the counts here)
     wbytes = lib.ffb6d_mean_shift_workspace_bytes(G, M)
     ws = torch.empty((max(wbytes, 1),), dtype=torch.uint8, device=dev)
     with torch.cuda.device(dev), _lib.traced("mean_shift", 16 * G * M, (G, M)):
         rc = lib.ffb6d_mean_shift_f32(
-            sets.data_ptr(), counts.data_ptr(), sets_per_count, G, M, int(max_count), float(bandwidth), int(max_iter),
+            sets.data_ptr(), counts.data_ptr(), sets_per_count, G, M, int(max_count or 0), float(bandwidth), int(max_iter),
             int(check_every), centers.data_ptr(), labels.data_ptr() if labels is not None else None,
             n_inside.data_ptr(), rounds.data_ptr(), ws.data_ptr(), wbytes, _stream(sets))
     _lib.check(rc, "ffb6d_mean_shift_f32")
@@ -98,19 +103,8 @@ MAX_CLUSTERS = 255     # cluster ids are u8 in the C ABI (include/ffb6d_pose.h)
 def vote_sets_inst(pcld, offsets, mask, inst, frame_of, class_of, inst_of):
     """vote_sets per instance: row p takes the points with mask == class_of[p] and inst == inst_of[p] (inst u8 [B,N], the
     map written by `instance_map`)."""
-    _need_gpu(pcld, offsets, mask, inst)
-    B, N, _ = pcld.shape
-    S = offsets.shape[1]
-    P = frame_of.numel()
-    pcld, offsets, mask = pcld.contiguous().float(), offsets.contiguous().float(), mask.contiguous()
-    sets = torch.empty((P * S, N, 4), dtype=torch.float32, device=pcld.device)
-    counts = torch.zeros((P,), dtype=torch.int32, device=pcld.device)
-    with torch.cuda.device(pcld.device), _lib.traced("vote_sets", 4 * (3 * B * N * (S + 1)) + 16 * P * S * N, (P, S, N)):
-        rc = _lib.load().ffb6d_vote_sets_inst_f32(
-            pcld.data_ptr(), offsets.data_ptr(), mask.data_ptr(), _mask_bits(mask), inst.data_ptr(), frame_of.data_ptr(),
-            class_of.data_ptr(), inst_of.data_ptr(), P, B, S, N, N, sets.data_ptr(), counts.data_ptr(), _stream(pcld))
-    _lib.check(rc, "ffb6d_vote_sets_inst_f32")
-    return sets, counts
+    _need_gpu(inst)
+    return _vote_sets(pcld, offsets, mask, frame_of, class_of, inst=inst, inst_of=inst_of)
 
 
 def mean_shift_multi(sets, counts, bandwidth, max_clusters, min_inside=1, max_iter=300, sets_per_count=1,
@@ -223,6 +217,47 @@ def best_fit_transform(A, B, device=None):
     return T[0].cpu().numpy()
 
 
+def _on_device(x):
+    return torch.is_tensor(x) and x.is_cuda
+
+
+def _mesh_tensors(mesh_kps, mesh_ctr, dev):
+    """host data, or device tensors as objinfo.ObjectInfo holds them -> f32 tensors on `dev`"""
+    f32 = lambda x: x.to(device=dev, dtype=torch.float32) if _on_device(x) else torch.as_tensor(np.asarray(x, np.float32), device=dev)   # noqa: E731
+    return f32(mesh_kps), f32(mesh_ctr)
+
+
+def _gate_distances(r_lst, classes_dev, classes_np, dev):
+    """0.8 radii (:98) of classes_dev when the radii live on the device (the same product, in double, no read-back), else of classes_np"""
+    if _on_device(r_lst):
+        return (r_lst.to(device=dev, dtype=torch.float64)[classes_dev.long() - 1] * 0.8).float()
+    return torch.tensor([np.float32(float(r_lst[c - 1]) * 0.8) for c in classes_np], dtype=torch.float32, device=dev)
+
+
+def _refine_mask(pcld, ctr_of, mask, centers, row_class, row_begin, row_dist):
+    """The centre mask filter (:83-108): a foreground point takes the class of the nearest centre among its frame's rows, within row_dist."""
+    B, N, _ = pcld.shape
+    new_mask = torch.empty_like(mask)
+    with torch.cuda.device(pcld.device):
+        rc = _lib.load().ffb6d_refine_mask_by_center(pcld.data_ptr(), ctr_of.data_ptr(), mask.data_ptr(), _mask_bits(mask),
+                                                     centers.data_ptr(), row_class.data_ptr(), row_begin.data_ptr(),
+                                                     row_dist.data_ptr(), B, N, new_mask.data_ptr(), _stream(pcld))
+    _lib.check(rc, "ffb6d_refine_mask_by_center")
+    return new_mask
+
+
+def _model_and_found(mesh_kps, mesh_ctr, row_class, kcenters, centers):
+    """model and found points [R,n_kps+1,3] of R rows: the keypoints, then the centre (cls_kps rows, :124,136)"""
+    R = row_class.shape[0]
+    found = torch.cat([kcenters.view(R, -1, 3), centers.view(R, 1, 3)], dim=1)
+    cls_long = row_class.long()
+    return torch.cat([mesh_kps[cls_long], mesh_ctr[cls_long].view(R, 1, 3)], dim=1), found
+
+
+def _fit(model, found, n_kps, use_ctr):
+    return best_fit_transform_batch(model, found) if use_ctr else best_fit_transform_batch(model[:, :n_kps], found[:, :n_kps])
+
+
 def solve_poses(pcld, mask, ctr_of, kp_of, mesh_kps, mesh_ctr, r_lst=None, use_ctr=True,
                 use_ctr_clus_flter=True, refine_mask=None, classes=None, radius=RADIUS, max_iter=300, stats=None, refine=None):
     """All objects of all frames at once.
@@ -244,27 +279,14 @@ def solve_poses(pcld, mask, ctr_of, kp_of, mesh_kps, mesh_ctr, r_lst=None, use_c
     B, N, _ = pcld.shape
     n_kps = kp_of.shape[1]
     dev = pcld.device
-    # host data, or device tensors as objinfo.ObjectInfo holds them
-    on_device = lambda x: torch.is_tensor(x) and x.is_cuda                                                                  # noqa: E731
-    mesh_kps = mesh_kps.to(device=dev, dtype=torch.float32) if on_device(mesh_kps) else torch.as_tensor(np.asarray(mesh_kps, np.float32), device=dev)
-    mesh_ctr = mesh_ctr.to(device=dev, dtype=torch.float32) if on_device(mesh_ctr) else torch.as_tensor(np.asarray(mesh_ctr, np.float32), device=dev)
-    n_cls = mesh_kps.shape[0]
+    mesh_kps, mesh_ctr = _mesh_tensors(mesh_kps, mesh_ctr, dev)
     if refine_mask is None:
         refine_mask = use_ctr_clus_flter and classes is None
     mask = mask.contiguous()
     mask_given = mask
     lib = _lib.load()
 
-    if classes is None:
-        present = torch.zeros((B, n_cls), dtype=torch.bool, device=dev)
-        present.scatter_(1, mask.clamp(0, n_cls - 1).long(), True)
-        present[:, 0] = False
-        present = present.cpu().numpy()
-        per_frame = [np.nonzero(present[b])[0] for b in range(B)]
-    else:
-        per_frame = [np.asarray(classes, np.int64) for _ in range(B)]
-    frame_np = np.concatenate([np.full(len(c), b, np.int32) for b, c in enumerate(per_frame)]) if B else np.zeros(0, np.int32)
-    class_np = np.concatenate(per_frame).astype(np.int32) if B else np.zeros(0, np.int32)
+    frame_np, class_np = _frame_class_pairs(mask, classes, B, mesh_kps.shape[0])
     P = len(class_np)
     if P == 0:
         return [(np.zeros(0, np.int64), np.zeros((0, 3, 4)), np.zeros((0, n_kps + 1, 3), np.float32)) for _ in range(B)]
@@ -282,17 +304,7 @@ def solve_poses(pcld, mask, ctr_of, kp_of, mesh_kps, mesh_ctr, r_lst=None, use_c
         begin = np.zeros(B + 1, np.int32)
         np.add.at(begin, frame_np + 1, 1)
         pair_begin = _i32(np.cumsum(begin), dev)
-        if on_device(r_lst):                                    # the same product, in double, without reading the radii back
-            max_dist = (r_lst.to(device=dev, dtype=torch.float64)[class_of.long() - 1] * 0.8).float()
-        else:
-            max_dist = torch.tensor([np.float32(float(r_lst[c - 1]) * 0.8) for c in class_np], dtype=torch.float32, device=dev)
-        new_mask = torch.empty_like(mask)
-        with torch.cuda.device(dev):
-            rc = lib.ffb6d_refine_mask_by_center(pcld.data_ptr(), ctr_of.data_ptr(), mask.data_ptr(), _mask_bits(mask),
-                                                 centers.data_ptr(), class_of.data_ptr(), pair_begin.data_ptr(),
-                                                 max_dist.data_ptr(), B, N, new_mask.data_ptr(), _stream(pcld))
-        _lib.check(rc, "ffb6d_refine_mask_by_center")
-        mask = new_mask
+        mask = _refine_mask(pcld, ctr_of, mask, centers, class_of, pair_begin, _gate_distances(r_lst, class_of, class_np, dev))
 
     # object centres (+ the labels of the winning centre cluster)
     sets, counts = vote_sets(pcld, ctr_of, mask, frame_of, class_of)
@@ -312,13 +324,8 @@ def solve_poses(pcld, mask, ctr_of, kp_of, mesh_kps, mesh_ctr, r_lst=None, use_c
     kcenters, _, _, rounds = mean_shift(ksets, kcounts, radius, max_iter, sets_per_count=n_kps, want_labels=False)
     if stats is not None:
         stats["rounds_kps"], stats["counts_kps"] = rounds, kcounts
-    found = torch.cat([kcenters.view(P, n_kps, 3), centers.view(P, 1, 3)], dim=1)          # cls_kps rows (:124,136)
-    cls_long = class_of.long()
-    model = torch.cat([mesh_kps[cls_long], mesh_ctr[cls_long].view(P, 1, 3)], dim=1)
-    if use_ctr:
-        T = best_fit_transform_batch(model, found)
-    else:
-        T = best_fit_transform_batch(model[:, :n_kps], found[:, :n_kps])
+    model, found = _model_and_found(mesh_kps, mesh_ctr, class_of, kcenters, centers)
+    T = _fit(model, found, n_kps, use_ctr)
     if refine is not None:
         from . import refine as _refine
         opts = dict(refine)
@@ -413,9 +420,7 @@ def _solve_instances(pcld, mask, ctr_of, kp_of, mesh_kps, mesh_ctr, max_instance
     n_kps = kp_of.shape[1]
     dev = pcld.device
     K = int(max_instances)
-    on_device = lambda x: torch.is_tensor(x) and x.is_cuda                                                                  # noqa: E731
-    mesh_kps = mesh_kps.to(device=dev, dtype=torch.float32) if on_device(mesh_kps) else torch.as_tensor(np.asarray(mesh_kps, np.float32), device=dev)
-    mesh_ctr = mesh_ctr.to(device=dev, dtype=torch.float32) if on_device(mesh_ctr) else torch.as_tensor(np.asarray(mesh_ctr, np.float32), device=dev)
+    mesh_kps, mesh_ctr = _mesh_tensors(mesh_kps, mesh_ctr, dev)
     mask = mask.contiguous()
     frame_np, class_np = _frame_class_pairs(mask, classes, B, mesh_kps.shape[0])
     P = len(class_np)
@@ -445,19 +450,10 @@ def _solve_instances(pcld, mask, ctr_of, kp_of, mesh_kps, mesh_ctr, max_instance
         per_frame = torch.zeros((B + 1,), dtype=torch.int64, device=dev)
         per_frame.index_add_(0, frame_of[p_of].long() + 1, torch.ones_like(p_of))
         row_begin = per_frame.cumsum(0).int()
-        if torch.is_tensor(r_lst) and r_lst.is_cuda:
-            row_dist = (r_lst.to(device=dev, dtype=torch.float64)[row_class.long() - 1] * 0.8).float()
-        else:
-            per_pair = torch.tensor([np.float32(float(r_lst[c - 1]) * 0.8) for c in class_np], dtype=torch.float32, device=dev)
-            row_dist = per_pair[p_of]
-        row_centers = centers[p_of, k_of].contiguous()
-        new_mask = torch.empty_like(mask)
-        with torch.cuda.device(dev):
-            rc = _lib.load().ffb6d_refine_mask_by_center(pcld.data_ptr(), ctr_of.data_ptr(), mask.data_ptr(), _mask_bits(mask),
-                                                         row_centers.data_ptr(), row_class.data_ptr(), row_begin.data_ptr(),
-                                                         row_dist.data_ptr(), B, N, new_mask.data_ptr(), _stream(pcld))
-        _lib.check(rc, "ffb6d_refine_mask_by_center")
-        mask = new_mask
+        row_dist = _gate_distances(r_lst, row_class, class_np, dev)                # per row from device radii, per pair from host radii
+        if not _on_device(r_lst):
+            row_dist = row_dist[p_of]
+        mask = _refine_mask(pcld, ctr_of, mask, centers[p_of, k_of].contiguous(), row_class, row_begin, row_dist)
 
     # 1. centre clusters of every (frame, class)
     sets, counts = vote_sets(pcld, ctr_of, mask, frame_of, class_of)
@@ -476,10 +472,8 @@ def _solve_instances(pcld, mask, ctr_of, kp_of, mesh_kps, mesh_ctr, max_instance
     kcenters, _, _, rounds = mean_shift(ksets, kcounts, radius, max_iter, sets_per_count=n_kps, want_labels=False)
     if stats is not None:
         stats["rounds_kps"], stats["counts_kps"] = rounds, kcounts
-    found = torch.cat([kcenters.view(E, n_kps, 3), centers[p_of, k_of].view(E, 1, 3)], dim=1)
-    cls_long = est_class.long()
-    model = torch.cat([mesh_kps[cls_long], mesh_ctr[cls_long].view(E, 1, 3)], dim=1)
-    T = best_fit_transform_batch(model, found) if use_ctr else best_fit_transform_batch(model[:, :n_kps], found[:, :n_kps])
+    model, found = _model_and_found(mesh_kps, mesh_ctr, est_class, kcenters, centers[p_of, k_of])
+    T = _fit(model, found, n_kps, use_ctr)
     out = dict(est_RT=T, est_class=est_class, est_frame=est_frame, est_instance=est_instance, est_score=score[p_of, k_of],
                kps=found, n_inside=n_in[p_of, k_of])
     if not refined:

@@ -81,6 +81,20 @@ def _problems(pcld, mask, poses, frame_of, class_of, models, keep):
     return pcld.contiguous().float(), mask.contiguous(), poses, frame_of, class_of, keep, P
 
 
+def _pair_outputs(P, N, dev):                                   # idx, d2, counts
+    return (torch.empty((P, N), dtype=torch.int32, device=dev), torch.empty((P, N), dtype=torch.float32, device=dev),
+            torch.empty((P,), dtype=torch.int32, device=dev))
+
+
+def _pose_outputs(P, dev):                                      # T, n_pairs, rms, iters
+    return (torch.empty((P, 3, 4), dtype=torch.float64, device=dev), torch.empty((P,), dtype=torch.int32, device=dev),
+            torch.empty((P,), dtype=torch.float32, device=dev), torch.empty((P,), dtype=torch.int32, device=dev))
+
+
+def _workspace(nbytes, dev):
+    return torch.empty((max(nbytes, 1),), dtype=torch.uint8, device=dev), nbytes
+
+
 def correspondences(pcld, mask, poses, frame_of, class_of, models, max_dist=float("inf"), keep=None):
     """One evaluation of steps 1-3: for the j-th scene point of problem p (the points of pcld[frame_of[p]] with
     mask == class_of[p], and keep != 0 when given, in index order) under poses[p] (f64 [P,3,4], model -> camera)
@@ -90,12 +104,9 @@ def correspondences(pcld, mask, poses, frame_of, class_of, models, max_dist=floa
     pcld, mask, poses, frame_of, class_of, keep, P = _problems(pcld, mask, poses, frame_of, class_of, models, keep)
     B, N, _ = pcld.shape
     dev = pcld.device
-    idx = torch.empty((P, N), dtype=torch.int32, device=dev)
-    d2 = torch.empty((P, N), dtype=torch.float32, device=dev)
-    counts = torch.empty((P,), dtype=torch.int32, device=dev)
+    idx, d2, counts = _pair_outputs(P, N, dev)
     lib = _lib.load()
-    wbytes = lib.ffb6d_icp_workspace_bytes(P, N)
-    ws = torch.empty((max(wbytes, 1),), dtype=torch.uint8, device=dev)
+    ws, wbytes = _workspace(lib.ffb6d_icp_workspace_bytes(P, N), dev)
     with torch.cuda.device(dev), _lib.traced("icp_correspond", 0, (P, N)):
         rc = lib.ffb6d_icp_correspond_f32(models.buf.data_ptr(), models.n_cls, models.total, pcld.data_ptr(), mask.data_ptr(),
                                           _mask_bits(mask), keep.data_ptr() if keep is not None else None, frame_of.data_ptr(),
@@ -117,13 +128,9 @@ def icp_refine(pcld, mask, poses, frame_of, class_of, models, max_iter=10, max_d
     pcld, mask, poses, frame_of, class_of, keep, P = _problems(pcld, mask, poses, frame_of, class_of, models, keep)
     B, N, _ = pcld.shape
     dev = pcld.device
-    T = torch.empty((P, 3, 4), dtype=torch.float64, device=dev)
-    n_pairs = torch.empty((P,), dtype=torch.int32, device=dev)
-    rms = torch.empty((P,), dtype=torch.float32, device=dev)
-    iters = torch.empty((P,), dtype=torch.int32, device=dev)
+    T, n_pairs, rms, iters = _pose_outputs(P, dev)
     lib = _lib.load()
-    wbytes = lib.ffb6d_icp_workspace_bytes(P, N)
-    ws = torch.empty((max(wbytes, 1),), dtype=torch.uint8, device=dev)
+    ws, wbytes = _workspace(lib.ffb6d_icp_workspace_bytes(P, N), dev)
     with torch.cuda.device(dev), _lib.traced("icp_refine", 0, (P, N, int(max_iter))):
         rc = lib.ffb6d_icp_refine_f32(models.buf.data_ptr(), models.n_cls, models.total, pcld.data_ptr(), mask.data_ptr(),
                                       _mask_bits(mask), keep.data_ptr() if keep is not None else None, frame_of.data_ptr(),
@@ -174,13 +181,10 @@ def correspondences_instances(pcld, mask, inst, poses, frame_of, class_of, inst_
                                                                                        models, mode, keep)
     B, N, _ = pcld.shape
     dev = pcld.device
-    idx = torch.empty((P, N), dtype=torch.int32, device=dev)
-    d2 = torch.empty((P, N), dtype=torch.float32, device=dev)
-    counts = torch.empty((P,), dtype=torch.int32, device=dev)
+    idx, d2, counts = _pair_outputs(P, N, dev)
     owner = torch.empty((P, N), dtype=torch.int32, device=dev)
     lib = _lib.load()
-    wbytes = lib.ffb6d_icp_inst_workspace_bytes(P, N, MODES[mode])
-    ws = torch.empty((max(wbytes, 1),), dtype=torch.uint8, device=dev)
+    ws, wbytes = _workspace(lib.ffb6d_icp_inst_workspace_bytes(P, N, MODES[mode]), dev)
     with torch.cuda.device(dev), _lib.traced("icp_correspond_inst", 0, (P, N)):
         rc = lib.ffb6d_icp_correspond_inst_f32(models.buf.data_ptr(), models.n_cls, models.total, pcld.data_ptr(), mask.data_ptr(),
                                                _mask_bits(mask), keep.data_ptr() if keep is not None else None,
@@ -204,14 +208,10 @@ def icp_refine_instances(pcld, mask, inst, poses, frame_of, class_of, inst_of, m
                                                                                        models, mode, keep)
     B, N, _ = pcld.shape
     dev = pcld.device
-    T = torch.empty((P, 3, 4), dtype=torch.float64, device=dev)
-    n_pairs = torch.empty((P,), dtype=torch.int32, device=dev)
-    rms = torch.empty((P,), dtype=torch.float32, device=dev)
-    iters = torch.empty((P,), dtype=torch.int32, device=dev)
+    T, n_pairs, rms, iters = _pose_outputs(P, dev)
     inst_out = torch.empty((B, N), dtype=torch.uint8, device=dev)
     lib = _lib.load()
-    wbytes = lib.ffb6d_icp_inst_workspace_bytes(P, N, MODES[mode])
-    ws = torch.empty((max(wbytes, 1),), dtype=torch.uint8, device=dev)
+    ws, wbytes = _workspace(lib.ffb6d_icp_inst_workspace_bytes(P, N, MODES[mode]), dev)
     with torch.cuda.device(dev), _lib.traced("icp_refine_inst", 0, (P, N, int(max_iter))):
         rc = lib.ffb6d_icp_refine_inst_f32(models.buf.data_ptr(), models.n_cls, models.total, pcld.data_ptr(), mask.data_ptr(),
                                            _mask_bits(mask), keep.data_ptr() if keep is not None else None,

@@ -43,8 +43,8 @@ int ffb6d_vote_sets_f32(const float* pcld, const float* offsets, const void* mas
  * neighbours within `bandwidth` (lowest index on ties), labels[j] = |point_j - centre| < bandwidth.
  *   centers f32 [G,3]; labels u8 [G,set_stride] or NULL; n_inside i32 [G] or NULL (size of the
  *   winning ball); iters i32 [G] or NULL (rounds made).  Sets with count 0 give centre (0,0,0).
- *   max_count: an upper bound on every count if the caller knows one (sizes the launch grids),
- *   0 = unknown (set_stride is used).
+ *   max_count: accepted (it must lie in [0, set_stride]) and ignored: the library sizes its own
+ *   launch grids from the counts.
  *   check_every > 0: every that many rounds the host reads back the convergence flags and stops
  *   launching when all sets are done (synchronises the stream); 0: all max_iter+1 rounds are
  *   enqueued (finished sets cost an empty launch) and the call never synchronises. */

@@ -1,6 +1,7 @@
 """CPU suite: the C-ABI library builds, loads and exports every symbol that include/*.h
 declares (no compute calls -- there is no GPU here), and the Python host layer fails
 loudly instead of falling back."""
+import ctypes
 import os
 import re
 
@@ -130,6 +131,27 @@ def test_pose_solver_workspace_and_form_switches_are_host_logic(native_lib):
     for setter in ("ffb6d_pose_set_fit_form", "ffb6d_pose_set_big_form"):
         getattr(native_lib, setter)(0)
         getattr(native_lib, setter)(1)
+
+
+def test_mean_shift_workspace_bytes_are_pinned(native_lib):
+    """The size query and the call share one layout (csrc/pose.hip mean_shift_layout); C callers allocate by these numbers.
+    Each is 2 * a256(16 G s) + a256(12 G) + a256(4 G) + a256(8 G) + 2 * a256(4 G s) + a256(20 G), a256 = round up to 256."""
+    from ffb6d_amd import _lib
+    for G, stride, want in ((1, 1, 2048), (3, 5, 2048), (40, 12288, 19663104), (320, 4097, 52455680)):
+        assert native_lib.ffb6d_mean_shift_workspace_bytes(G, stride) == want
+        assert native_lib.ffb6d_mean_shift_multi_workspace_bytes(G, stride) == want
+    for G, stride in ((0, 5), (-1, 5), (3, 0), (3, -7)):
+        assert native_lib.ffb6d_mean_shift_workspace_bytes(G, stride) == 0
+        assert native_lib.ffb6d_mean_shift_multi_workspace_bytes(G, stride) == 0
+    # one byte short: refused before anything touches a device (the pointers are never read)
+    G, stride = 3, 5
+    need = native_lib.ffb6d_mean_shift_workspace_bytes(G, stride)
+    host = ctypes.create_string_buffer(64)
+    ptr = ctypes.addressof(host)
+    rc = native_lib.ffb6d_mean_shift_f32(ptr, ptr, 1, G, stride, 0, 0.04, 10, 0, ptr, None, None, None, ptr, need - 1, None)
+    assert rc == -3 and f"workspace {need - 1} < {need} bytes" in _lib.last_error()              # FFB6D_ERR_WORKSPACE
+    rc = native_lib.ffb6d_mean_shift_multi_f32(ptr, ptr, 1, G, stride, 0, 0.04, 10, 0, 4, 1, ptr, ptr, ptr, ptr, None, ptr, need - 1, None)
+    assert rc == -3 and f"workspace {need - 1} < {need} bytes" in _lib.last_error()
 
 
 def test_argument_errors_are_reported_without_a_gpu(native_lib):
