@@ -1,5 +1,6 @@
-"""Builds scripts/icp_instances_sanitize.cpp with csrc/errors.hip + csrc/icp.hip for the HOST against the SIMT emulator (the
-substitutions of tests/simt/build.py) under -fsanitize=address,undefined, and runs it.  No GPU, no Python extension involved:
+"""Builds scripts/icp_instances_sanitize.cpp with csrc/errors.hip + csrc/icp.hip for the HOST against the SIMT emulator (flags,
+include paths and substitutions of tests/simt/build.py) under -fsanitize=address,undefined, and runs it.  An instrumented build
+of its own: the emulator's cached objects carry no sanitizer.  No GPU, no Python extension involved:
     python scripts/icp_instances_sanitize.py
 Exit status 0 and the program's "ok" line = no finding."""
 import os
@@ -11,17 +12,15 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 from tests.simt import build as sb      # noqa: E402
 
+SANITIZE = ["-fno-omit-frame-pointer", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined"]
+
 
 def main():
-    os.makedirs(sb.OUT, exist_ok=True)
     srcs = [sb.transformed(n) for n in ("errors.hip", "icp.hip")] + [os.path.join(sb.HERE, "simt.cpp"),
                                                                     os.path.join(ROOT, "scripts", "icp_instances_sanitize.cpp")]
     with tempfile.TemporaryDirectory() as tmp:
         exe = os.path.join(tmp, "icp_instances_sanitize")
-        cmd = [sb.CLANG, "-x", "c++", "-std=c++17", "-O1", "-g", "-fno-omit-frame-pointer", "-fsanitize=address,undefined",
-               "-fno-sanitize-recover=undefined", "-ffp-contract=off", "-Wno-unused-value", "-Wno-psabi", "-Wno-unknown-attributes",
-               "-I" + os.path.join(sb.HERE, "fake"), "-I" + sb.HERE, "-I" + os.path.join(ROOT, "include"), "-I" + sb.CSRC] + srcs + ["-o", exe]
-        subprocess.run(cmd, check=True)
+        subprocess.run([sb.CLANG] + sb.FLAGS + SANITIZE + sb.INCLUDES + srcs + ["-o", exe], check=True)
         return subprocess.run([exe]).returncode
 
 

@@ -4,7 +4,6 @@ fiber-per-thread emulator) and lift the GPU guards of the host wrappers so that 
 context, current stream).  Test infrastructure: used by the `emu` fixture (tests/conftest.py) and by worker processes of the
 multi-process CPU tests."""
 import contextlib
-import ctypes
 
 
 def bind(mp):
@@ -13,11 +12,7 @@ def bind(mp):
 
     from ffb6d_amd import _lib, ops, ops_cl, ops_pm, pose
     from tests.simt import build
-    lib = ctypes.CDLL(build.build())
-    for name, (res, args) in _lib.SIGNATURES.items():        # every entry point the emulated sources export
-        if hasattr(lib, name):
-            fn = getattr(lib, name)
-            fn.restype, fn.argtypes = res, args
+    lib = build.load()
     mp.setattr(_lib, "_LIB", lib)
     for mod in (ops, ops_cl, ops_pm, pose):
         mp.setattr(mod, "_need_gpu", lambda *ts: None)

@@ -2,38 +2,20 @@
 compiled for the host and run through the C ABI of include/ffb6d_bop.h.  mssd2, mspd2, the counts and vsd equal the numpy
 restatement (tests/bop_ref.py) bit for bit; argument errors return their code and write nothing; guard values around the outputs
 stay intact."""
-import ctypes
-import os
-import subprocess
-
 import numpy as np
 import pytest
 
 import bop_ref
 import render_ref
+from tests.simt.build import load, ptr as _p
 
-ENTRY_POINTS = ("ffb6d_last_error", "ffb6d_render_workspace_bytes", "ffb6d_render_f32", "ffb6d_bop_mssd_mspd_workspace_bytes",
-                "ffb6d_bop_mssd_mspd_f64", "ffb6d_bop_vsd_workspace_bytes", "ffb6d_bop_vsd_f32")
 GUARD = 8                       # guard entries on either side of an output
 
 
 @pytest.fixture(scope="module")
-def emu_bop(tmp_path_factory):
-    """errors.hip + render.hip + bop_eval.hip compiled for the host against the emulator, with the flags of tests/simt/build.py."""
-    from ffb6d_amd import _lib
-    from tests.simt import build as sb
-    os.makedirs(sb.OUT, exist_ok=True)
-    out = str(tmp_path_factory.mktemp("simt_bop") / "libsimt_bop.so")
-    srcs = [sb.transformed(n) for n in ("errors.hip", "render.hip", "bop_eval.hip")] + [os.path.join(sb.HERE, "simt.cpp")]
-    cmd = [sb.CLANG, "-x", "c++", "-std=c++17", "-O1", "-g", "-fPIC", "-shared", "-ffp-contract=off", "-Wno-unused-value",
-           "-Wno-psabi", "-Wno-unknown-attributes", "-I" + os.path.join(sb.HERE, "fake"), "-I" + sb.HERE,
-           "-I" + os.path.join(sb.ROOT, "include"), "-I" + sb.CSRC] + srcs + ["-o", out]
-    subprocess.run(cmd, check=True)
-    lib = ctypes.CDLL(out)
-    for name in ENTRY_POINTS:
-        fn = getattr(lib, name)
-        fn.restype, fn.argtypes = _lib.SIGNATURES[name]
-    return lib
+def emu_bop():
+    """the emulated library (tests/simt/build.py)"""
+    return load()
 
 
 @pytest.fixture(scope="module")
@@ -46,10 +28,6 @@ def case():
         for v in r["want"]:
             v.setflags(write=False)
     return c
-
-
-def _p(a):
-    return a.ctypes.data if a is not None else None
 
 
 def guarded(shape, dtype, fill):

@@ -2,19 +2,13 @@
 forms and hand-worked matchings, and the unmodified csrc/bop_scene.hip on the SIMT emulator (tests/simt) through the C ABI: every
 output equals the restatement as bits, guard values around the outputs stay intact, a poisoned workspace changes nothing, argument
 errors return their code and write nothing."""
-import ctypes
-import os
-import subprocess
-
 import numpy as np
 import pytest
 
 import bop_scene_ref as ref
 import render_ref
 from test_bop_emu_cpu import _p, bits, emu_render_alone, guarded, guards_intact
-
-ENTRY_POINTS = ("ffb6d_last_error", "ffb6d_render_workspace_bytes", "ffb6d_render_f32", "ffb6d_bop_visib_workspace_bytes", "ffb6d_bop_visib_f32",
-                "ffb6d_bop_match_check", "ffb6d_bop_match_workspace_bytes", "ffb6d_bop_match_f64")
+from tests.simt.build import load
 
 # a camera whose principal point is the pixel (row 12, column 16) of a 24 x 32 frame, and a rectangle at depth 1 whose edges project
 # to the half pixels 4.5 / 20.5 (columns 5 .. 20) and 2.5 / 12.5 (rows 3 .. 12): 160 pixels whatever the rasteriser's tie rule
@@ -136,22 +130,9 @@ def test_pair_rows_groups_by_frame_and_class():
 
 # ---- the unmodified kernels on the SIMT emulator ----------------------------------------------------------------------------------
 @pytest.fixture(scope="module")
-def emu_scene(tmp_path_factory):
-    """errors.hip + render.hip + bop_scene.hip compiled for the host against the emulator, with the flags of tests/simt/build.py."""
-    from ffb6d_amd import _lib
-    from tests.simt import build as sb
-    os.makedirs(sb.OUT, exist_ok=True)
-    out = str(tmp_path_factory.mktemp("simt_bop_scene") / "libsimt_bop_scene.so")
-    srcs = [sb.transformed(n) for n in ("errors.hip", "render.hip", "bop_scene.hip")] + [os.path.join(sb.HERE, "simt.cpp")]
-    cmd = [sb.CLANG, "-x", "c++", "-std=c++17", "-O1", "-g", "-fPIC", "-shared", "-ffp-contract=off", "-Wno-unused-value",
-           "-Wno-psabi", "-Wno-unknown-attributes", "-I" + os.path.join(sb.HERE, "fake"), "-I" + sb.HERE,
-           "-I" + os.path.join(sb.ROOT, "include"), "-I" + sb.CSRC] + srcs + ["-o", out]
-    subprocess.run(cmd, check=True)
-    lib = ctypes.CDLL(out)
-    for name in ENTRY_POINTS:
-        fn = getattr(lib, name)
-        fn.restype, fn.argtypes = _lib.SIGNATURES[name]
-    return lib
+def emu_scene():
+    """the emulated library (tests/simt/build.py)"""
+    return load()
 
 
 def call_visib(lib, v, out_info, out_fract, out_mask, ws=None, **kw):

@@ -4,38 +4,23 @@ Pillow's bytes, through each of the three access widths the launcher chooses fro
 offsets 0, 4 and 1 of an aligned buffer where its size allows the wider forms); a batch that mixes a copied frame, a frame without
 contrast and frames with the contrast in different positions equals the restatement; argument errors return their code and leave a
 pre-filled output untouched; a short workspace is refused; bad records are refused by the host check and copied by the kernels."""
-import ctypes
 import json
 import os
-import subprocess
 
 import numpy as np
 import pytest
 
 import color_jitter_ref as ref
+from tests.simt.build import load
 
-ENTRY_POINTS = ("ffb6d_last_error", "ffb6d_jitter_frames_check", "ffb6d_color_jitter_workspace_bytes", "ffb6d_color_jitter_u8")
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "color_jitter.npz")
 FILL = 0xA5
 
 
 @pytest.fixture(scope="module")
-def emu_jitter(tmp_path_factory):
-    """errors.hip + color_jitter.hip compiled for the host against the emulator, with the flags of tests/simt/build.py."""
-    from ffb6d_amd import _lib
-    from tests.simt import build as sb
-    os.makedirs(sb.OUT, exist_ok=True)
-    out = str(tmp_path_factory.mktemp("simt_jitter") / "libsimt_jitter.so")
-    srcs = [sb.transformed(n) for n in ("errors.hip", "color_jitter.hip")] + [os.path.join(sb.HERE, "simt.cpp")]
-    cmd = [sb.CLANG, "-x", "c++", "-std=c++17", "-O1", "-g", "-fPIC", "-shared", "-ffp-contract=off", "-Wno-unused-value",
-           "-Wno-psabi", "-Wno-unknown-attributes", "-I" + os.path.join(sb.HERE, "fake"), "-I" + sb.HERE,
-           "-I" + os.path.join(sb.ROOT, "include"), "-I" + sb.CSRC] + srcs + ["-o", out]
-    subprocess.run(cmd, check=True)
-    lib = ctypes.CDLL(out)
-    for name in ENTRY_POINTS:
-        fn = getattr(lib, name)
-        fn.restype, fn.argtypes = _lib.SIGNATURES[name]
-    return lib
+def emu_jitter():
+    """the emulated library (tests/simt/build.py)"""
+    return load()
 
 
 @pytest.fixture(scope="module")

@@ -1,16 +1,15 @@
 """Pose evaluation without a GPU (ffb6d_amd/evaluate.py, csrc/pose_eval.hip): the AUC arithmetic against the reference's
 own results (tests/golden/eval_small.npz, make_golden_eval.py) bit for bit, the workspace formula of include/ffb6d_eval.h,
 and the ADD / ADD-S kernel itself run through the SIMT emulator (tests/simt) on small cases against a float64 restatement."""
-import ctypes
 import importlib.util
 import os
-import subprocess
 
 import numpy as np
 import pytest
 
 from conftest import GOLDEN
 from ffb6d_amd import evaluate
+from tests.simt.build import load
 
 spec = importlib.util.spec_from_file_location("make_golden_eval", os.path.join(GOLDEN, "make_golden_eval.py"))
 gen = importlib.util.module_from_spec(spec)
@@ -93,22 +92,9 @@ def test_workspace_formula(native_lib):
 
 # ---- the kernel on the SIMT emulator ---------------------------------------------------------------------------
 @pytest.fixture(scope="module")
-def emu_eval(tmp_path_factory):
-    """errors.hip + pose_eval.hip compiled for the host against the emulator, with the flags of tests/simt/build.py."""
-    from ffb6d_amd import _lib
-    from tests.simt import build as sb
-    os.makedirs(sb.OUT, exist_ok=True)
-    out = str(tmp_path_factory.mktemp("simt_eval") / "libsimt_eval.so")
-    srcs = [sb.transformed(n) for n in ("errors.hip", "pose_eval.hip")] + [os.path.join(sb.HERE, "simt.cpp")]
-    cmd = [sb.CLANG, "-x", "c++", "-std=c++17", "-O1", "-g", "-fPIC", "-shared", "-ffp-contract=off", "-Wno-unused-value",
-           "-Wno-psabi", "-Wno-unknown-attributes", "-I" + os.path.join(sb.HERE, "fake"), "-I" + sb.HERE,
-           "-I" + os.path.join(sb.ROOT, "include"), "-I" + sb.CSRC] + srcs + ["-o", out]
-    subprocess.run(cmd, check=True)
-    lib = ctypes.CDLL(out)
-    for name in ("ffb6d_last_error", "ffb6d_pose_add_adds_workspace_bytes", "ffb6d_pose_add_adds_f32"):
-        fn = getattr(lib, name)
-        fn.restype, fn.argtypes = _lib.SIGNATURES[name]
-    return lib
+def emu_eval():
+    """the emulated library (tests/simt/build.py)"""
+    return load()
 
 
 def ref_add_adds(p, pred, gt):

@@ -4,38 +4,20 @@ and with m above every n; both forms are forced in turn and both start modes are
 restatement (tests/fps_ref.py) bit for bit; argument errors return their code and write nothing.  The box statistics are held
 against the restatement and against hand-computed vectors: the reference's MeshUtils imports OpenCV and plyfile, which the build
 image lacks, so nothing of it can be run to record a golden."""
-import ctypes
-import os
-import subprocess
-
 import numpy as np
 import pytest
 
 import fps_ref
+from tests.simt.build import load, ptr as _p
 
-ENTRY_POINTS = ("ffb6d_last_error", "ffb6d_fps_resident_capacity", "ffb6d_fps_set_form", "ffb6d_fps_workspace_bytes",
-                "ffb6d_fps_f32", "ffb6d_box_info_f32")
 SIZES = (0, 1, 63, 64, 65, 300)
 FILL = 7
 
 
 @pytest.fixture(scope="module")
-def emu_fps(tmp_path_factory):
-    """errors.hip + fps.hip compiled for the host against the emulator, with the flags of tests/simt/build.py."""
-    from ffb6d_amd import _lib
-    from tests.simt import build as sb
-    os.makedirs(sb.OUT, exist_ok=True)
-    out = str(tmp_path_factory.mktemp("simt_fps") / "libsimt_fps.so")
-    srcs = [sb.transformed(n) for n in ("errors.hip", "fps.hip")] + [os.path.join(sb.HERE, "simt.cpp")]
-    cmd = [sb.CLANG, "-x", "c++", "-std=c++17", "-O1", "-g", "-fPIC", "-shared", "-ffp-contract=off", "-Wno-unused-value",
-           "-Wno-psabi", "-Wno-unknown-attributes", "-I" + os.path.join(sb.HERE, "fake"), "-I" + sb.HERE,
-           "-I" + os.path.join(sb.ROOT, "include"), "-I" + sb.CSRC] + srcs + ["-o", out]
-    subprocess.run(cmd, check=True)
-    lib = ctypes.CDLL(out)
-    for name in ENTRY_POINTS:
-        fn = getattr(lib, name)
-        fn.restype, fn.argtypes = _lib.SIGNATURES[name]
-    return lib
+def emu_fps():
+    """the emulated library (tests/simt/build.py)"""
+    return load()
 
 
 @pytest.fixture(scope="module")
@@ -45,10 +27,6 @@ def sets():
     for a in out:
         a.setflags(write=False)
     return out
-
-
-def _p(a):
-    return a.ctypes.data if a is not None else None
 
 
 def fresh(S, m):

@@ -3,40 +3,19 @@ the C ABI of include/ffb6d_orb.h.  Three frames of different content go in one c
 image); 48 x 64 and 37 x 53 pixels, 1 and 3 levels, edge 4, quotas above and well below the candidate counts, so that the top-n
 cut and its tie rule are exercised.  count, kps and resp, the lifted slots and the compacted point sets equal the numpy restatement
 (tests/orb_ref.py) bit for bit; argument errors return their code and write nothing."""
-import ctypes
-import os
-import subprocess
-
 import numpy as np
 import pytest
 
 import orb_ref
+from tests.simt.build import load, ptr as _p
 
-ENTRY_POINTS = ("ffb6d_last_error", "ffb6d_orb_workspace_bytes", "ffb6d_orb_detect_u8", "ffb6d_orb_lift_f32", "ffb6d_orb_compact_f32")
 FILL = 7
 
 
 @pytest.fixture(scope="module")
-def emu_orb(tmp_path_factory):
-    """errors.hip + orb.hip compiled for the host against the emulator, with the flags of tests/simt/build.py."""
-    from ffb6d_amd import _lib
-    from tests.simt import build as sb
-    os.makedirs(sb.OUT, exist_ok=True)
-    out = str(tmp_path_factory.mktemp("simt_orb") / "libsimt_orb.so")
-    srcs = [sb.transformed(n) for n in ("errors.hip", "orb.hip")] + [os.path.join(sb.HERE, "simt.cpp")]
-    cmd = [sb.CLANG, "-x", "c++", "-std=c++17", "-O1", "-g", "-fPIC", "-shared", "-ffp-contract=off", "-Wno-unused-value",
-           "-Wno-psabi", "-Wno-unknown-attributes", "-I" + os.path.join(sb.HERE, "fake"), "-I" + sb.HERE,
-           "-I" + os.path.join(sb.ROOT, "include"), "-I" + sb.CSRC] + srcs + ["-o", out]
-    subprocess.run(cmd, check=True)
-    lib = ctypes.CDLL(out)
-    for name in ENTRY_POINTS:
-        fn = getattr(lib, name)
-        fn.restype, fn.argtypes = _lib.SIGNATURES[name]
-    return lib
-
-
-def _p(a):
-    return a.ctypes.data if a is not None else None
+def emu_orb():
+    """the emulated library (tests/simt/build.py)"""
+    return load()
 
 
 def fresh(F, Q):

@@ -3,42 +3,19 @@ the unmodified kernel source compiled for the host, run through the C ABI on tin
 (tests/pose_instances_ref.py) run on the kernel's OWN converged points (ffb6d_pose_set_converged_out) -- cluster ids, ball sizes and
 cluster counts equal, centres bit-equal to converged points; cluster 1 against the single fit as bits; the instance map and the
 per-instance vote sets."""
-import ctypes
-import os
-import subprocess
-
 import numpy as np
 import pytest
 
 import pose_instances_ref as ref
+from tests.simt.build import load, ptr as _p
 
-NAMES = ("ffb6d_last_error", "ffb6d_mean_shift_workspace_bytes", "ffb6d_mean_shift_f32", "ffb6d_mean_shift_multi_workspace_bytes",
-         "ffb6d_mean_shift_multi_f32", "ffb6d_pose_set_converged_out", "ffb6d_set_clusters_to_points", "ffb6d_vote_sets_inst_f32",
-         "ffb6d_vote_sets_f32")
 BW = 0.04
 
 
 @pytest.fixture(scope="module")
-def emu_pose(tmp_path_factory):
-    """errors.hip + pose.hip compiled for the host against the emulator, with the flags of tests/simt/build.py."""
-    from ffb6d_amd import _lib
-    from tests.simt import build as sb
-    os.makedirs(sb.OUT, exist_ok=True)
-    out = str(tmp_path_factory.mktemp("simt_pose") / "libsimt_pose.so")
-    srcs = [sb.transformed(n) for n in ("errors.hip", "pose.hip")] + [os.path.join(sb.HERE, "simt.cpp")]
-    cmd = [sb.CLANG, "-x", "c++", "-std=c++17", "-O1", "-g", "-fPIC", "-shared", "-ffp-contract=off", "-Wno-unused-value",
-           "-Wno-psabi", "-Wno-unknown-attributes", "-I" + os.path.join(sb.HERE, "fake"), "-I" + sb.HERE,
-           "-I" + os.path.join(sb.ROOT, "include"), "-I" + sb.CSRC] + srcs + ["-o", out]
-    subprocess.run(cmd, check=True)
-    lib = ctypes.CDLL(out)
-    for name in NAMES:
-        fn = getattr(lib, name)
-        fn.restype, fn.argtypes = _lib.SIGNATURES[name]
-    return lib
-
-
-def _p(a):
-    return a.ctypes.data
+def emu_pose():
+    """the emulated library (tests/simt/build.py)"""
+    return load()
 
 
 def pack(clouds, stride):

@@ -1,41 +1,20 @@
 """csrc/icp.hip on the SIMT emulator (tests/simt), without a GPU: the unmodified kernel source compiled for the host, run through
 the C ABI of include/ffb6d_refine.h on tiny ragged problems and held against the numpy restatement (tests/icp_ref.py) -- the
 correspondences as bits in both forms of the search, the loop within the bar of the device test, degenerate problems as bits."""
-import ctypes
-import os
-import subprocess
-
 import numpy as np
 import pytest
 
 import icp_ref
 from ffb6d_amd import synth
+from tests.simt.build import load, ptr as _p
 
 INF = float("inf")
 
 
 @pytest.fixture(scope="module")
-def emu_icp(tmp_path_factory):
-    """errors.hip + icp.hip compiled for the host against the emulator, with the flags of tests/simt/build.py."""
-    from ffb6d_amd import _lib
-    from tests.simt import build as sb
-    os.makedirs(sb.OUT, exist_ok=True)
-    out = str(tmp_path_factory.mktemp("simt_icp") / "libsimt_icp.so")
-    srcs = [sb.transformed(n) for n in ("errors.hip", "icp.hip")] + [os.path.join(sb.HERE, "simt.cpp")]
-    cmd = [sb.CLANG, "-x", "c++", "-std=c++17", "-O1", "-g", "-fPIC", "-shared", "-ffp-contract=off", "-Wno-unused-value",
-           "-Wno-psabi", "-Wno-unknown-attributes", "-I" + os.path.join(sb.HERE, "fake"), "-I" + sb.HERE,
-           "-I" + os.path.join(sb.ROOT, "include"), "-I" + sb.CSRC] + srcs + ["-o", out]
-    subprocess.run(cmd, check=True)
-    lib = ctypes.CDLL(out)
-    for name in ("ffb6d_last_error", "ffb6d_icp_prepared_bytes", "ffb6d_icp_prepare", "ffb6d_icp_workspace_bytes", "ffb6d_icp_set_form",
-                 "ffb6d_icp_set_pair_counter", "ffb6d_icp_correspond_f32", "ffb6d_icp_refine_f32"):
-        fn = getattr(lib, name)
-        fn.restype, fn.argtypes = _lib.SIGNATURES[name]
-    return lib
-
-
-def _p(a):
-    return a.ctypes.data
+def emu_icp():
+    """the emulated library (tests/simt/build.py)"""
+    return load()
 
 
 def tiny_case():

@@ -2,39 +2,21 @@
 ffb6d_icp_refine_inst_f32 through the C ABI on the tiny ragged case of tests/icp_inst_ref.py (`instances_case`), held against the
 numpy restatement -- the single step as bits in both modes and all forms of the search, the loop within the bar of the device
 test, the anchors to the class calls as bits, degenerate problems as bits."""
-import ctypes
-import os
-import subprocess
-
 import numpy as np
 import pytest
 
 import icp_inst_ref as iref
 from test_refine_emu_cpu import _canon, _p, prepare
+from tests.simt.build import load
 
 INF = float("inf")
 MODE = {"map": 0, "nearest": 1}
-NAMES = ("ffb6d_last_error", "ffb6d_icp_prepared_bytes", "ffb6d_icp_prepare", "ffb6d_icp_workspace_bytes", "ffb6d_icp_set_form",
-         "ffb6d_icp_set_pair_counter", "ffb6d_icp_correspond_f32", "ffb6d_icp_refine_f32", "ffb6d_icp_inst_workspace_bytes",
-         "ffb6d_icp_correspond_inst_f32", "ffb6d_icp_refine_inst_f32")
 
 
 @pytest.fixture(scope="module")
-def emu(tmp_path_factory):
-    """errors.hip + icp.hip compiled for the host against the emulator, with the flags of tests/simt/build.py."""
-    from ffb6d_amd import _lib
-    from tests.simt import build as sb
-    os.makedirs(sb.OUT, exist_ok=True)
-    out = str(tmp_path_factory.mktemp("simt_icp_inst") / "libsimt_icp_inst.so")
-    srcs = [sb.transformed(n) for n in ("errors.hip", "icp.hip")] + [os.path.join(sb.HERE, "simt.cpp")]
-    cmd = [sb.CLANG, "-x", "c++", "-std=c++17", "-O1", "-g", "-fPIC", "-shared", "-ffp-contract=off", "-Wno-unused-value",
-           "-Wno-psabi", "-Wno-unknown-attributes", "-I" + os.path.join(sb.HERE, "fake"), "-I" + sb.HERE,
-           "-I" + os.path.join(sb.ROOT, "include"), "-I" + sb.CSRC] + srcs + ["-o", out]
-    subprocess.run(cmd, check=True)
-    lib = ctypes.CDLL(out)
-    for name in NAMES:
-        fn = getattr(lib, name)
-        fn.restype, fn.argtypes = _lib.SIGNATURES[name]
+def emu():
+    """the emulated library (tests/simt/build.py); the search form is back at its default when the module is over"""
+    lib = load()
     yield lib
     lib.ffb6d_icp_set_form(0)
 

@@ -1,36 +1,19 @@
 """csrc/render.hip on the SIMT emulator (tests/simt), without a GPU: the unmodified kernel source compiled for the host and run
 through the C ABI of include/ffb6d_render.h on the small scene of tests/render_ref.py.  Every output equals the numpy
 restatement bit for bit, in both forms of the raster pass; argument errors return their code and write nothing."""
-import ctypes
-import os
-import subprocess
-
 import numpy as np
 import pytest
 
 import render_ref
+from tests.simt.build import load, ptr as _p
 
-ENTRY_POINTS = ("ffb6d_last_error", "ffb6d_render_workspace_bytes", "ffb6d_render_set_form", "ffb6d_render_f32")
 OUTPUTS = ("rgb", "depth", "label", "inst", "face", "visible")
 
 
 @pytest.fixture(scope="module")
-def emu_render(tmp_path_factory):
-    """errors.hip + render.hip compiled for the host against the emulator, with the flags of tests/simt/build.py."""
-    from ffb6d_amd import _lib
-    from tests.simt import build as sb
-    os.makedirs(sb.OUT, exist_ok=True)
-    out = str(tmp_path_factory.mktemp("simt_render") / "libsimt_render.so")
-    srcs = [sb.transformed(n) for n in ("errors.hip", "render.hip")] + [os.path.join(sb.HERE, "simt.cpp")]
-    cmd = [sb.CLANG, "-x", "c++", "-std=c++17", "-O1", "-g", "-fPIC", "-shared", "-ffp-contract=off", "-Wno-unused-value",
-           "-Wno-psabi", "-Wno-unknown-attributes", "-I" + os.path.join(sb.HERE, "fake"), "-I" + sb.HERE,
-           "-I" + os.path.join(sb.ROOT, "include"), "-I" + sb.CSRC] + srcs + ["-o", out]
-    subprocess.run(cmd, check=True)
-    lib = ctypes.CDLL(out)
-    for name in ENTRY_POINTS:
-        fn = getattr(lib, name)
-        fn.restype, fn.argtypes = _lib.SIGNATURES[name]
-    return lib
+def emu_render():
+    """the emulated library (tests/simt/build.py)"""
+    return load()
 
 
 @pytest.fixture(scope="module")
@@ -40,10 +23,6 @@ def scene():
     for v in want.values():
         v.setflags(write=False)
     return s, want
-
-
-def _p(a):
-    return a.ctypes.data if a is not None else None
 
 
 def fresh_outputs(n_inst, B, H, W, fill=7):

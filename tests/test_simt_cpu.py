@@ -316,6 +316,21 @@ def test_emulated_library_reports_argument_errors_like_the_product(emu):
     assert ops.ACT_RELU == 1
 
 
+def test_emulated_library_exports_every_entry_point_but_those_of_the_excluded_sources(emu):
+    """every csrc/*.hip is in the emulated library except tests/simt/build.py's EXCLUDED: the names of _lib.SIGNATURES it lacks
+    are exactly the `extern "C"` entry points those files define"""
+    import re
+
+    from tests.simt import build
+    assert list(build.EXCLUDED) == ["mlp_pm_split.hip"]
+    defined = set()
+    for name in build.EXCLUDED:
+        with open(os.path.join(build.CSRC, name)) as fh:
+            defined |= set(re.findall(r'^extern "C" \w+ (ffb6d_\w+)\(', fh.read(), re.M))
+    assert defined and all(n.startswith("ffb6d_mlp_pm_split_") for n in defined)
+    assert {n for n in _lib.SIGNATURES if not hasattr(emu, n)} == defined
+
+
 # ---------------------------------------------------------------------------------------------------------------
 # launch paths of the per-thread kernels (csrc/upconv.hip, csrc/posenc.hip): grid arithmetic, XCD-band workgroup order and
 # kernel-form selection run here exactly as on the GPU (their bodies alone: tests/test_hostsim_cpu.py)

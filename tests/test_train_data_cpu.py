@@ -2,17 +2,16 @@
 log of the reference's own rgb_add_noise (tests/golden/train_small.json, make_golden_train.py), the motion-blur tap lists, and
 the four kernels run through the SIMT emulator (tests/simt) on tiny inputs against the reference's own get_pose_gt_info
 (tests/golden/train_small.npz) and the restatements of tests/train_data_ref.py."""
-import ctypes
 import importlib.util
 import json
 import os
-import subprocess
 
 import numpy as np
 import pytest
 
 from conftest import GOLDEN
 from ffb6d_amd import train_data
+from tests.simt.build import load, ptr as _p
 from train_data_ref import filter_ref, hsv_jitter_ref, pose_targets_ref
 
 spec = importlib.util.spec_from_file_location("make_golden_train", os.path.join(GOLDEN, "make_golden_train.py"))
@@ -124,26 +123,9 @@ def test_motion_blur_taps_identity_when_the_kernel_is_empty():
 
 # ---- the kernels on the SIMT emulator ---------------------------------------------------------------------------
 @pytest.fixture(scope="module")
-def emu_train(tmp_path_factory):
-    """errors.hip + train_data.hip compiled for the host against the emulator, with the flags of tests/simt/build.py."""
-    from ffb6d_amd import _lib
-    from tests.simt import build as sb
-    os.makedirs(sb.OUT, exist_ok=True)
-    out = str(tmp_path_factory.mktemp("simt_train") / "libsimt_train.so")
-    srcs = [sb.transformed(n) for n in ("errors.hip", "train_data.hip")] + [os.path.join(sb.HERE, "simt.cpp")]
-    cmd = [sb.CLANG, "-x", "c++", "-std=c++17", "-O1", "-g", "-fPIC", "-shared", "-ffp-contract=off", "-Wno-unused-value",
-           "-Wno-psabi", "-Wno-unknown-attributes", "-I" + os.path.join(sb.HERE, "fake"), "-I" + sb.HERE,
-           "-I" + os.path.join(sb.ROOT, "include"), "-I" + sb.CSRC] + srcs + ["-o", out]
-    subprocess.run(cmd, check=True)
-    lib = ctypes.CDLL(out)
-    for name in ("ffb6d_last_error", "ffb6d_pose_targets", "ffb6d_rgb_hsv_jitter", "ffb6d_rgb_stencil", "ffb6d_add_real_back"):
-        fn = getattr(lib, name)
-        fn.restype, fn.argtypes = _lib.SIGNATURES[name]
-    return lib
-
-
-def _p(a):
-    return a.ctypes.data
+def emu_train():
+    """the emulated library (tests/simt/build.py)"""
+    return load()
 
 
 def emu_pose_targets(lib, cld, choose, label_img, cls_ids, RTs, kps, ctr):

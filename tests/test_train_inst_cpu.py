@@ -2,43 +2,21 @@
 through the SIMT emulator (tests/simt) against the numpy restatement of tests/train_inst_ref.py bit for bit, against the existing
 ffb6d_pose_targets where both are defined, and on the case that existing call cannot represent; guard words around every
 output, a workspace full of NaN bytes, and every argument error."""
-import ctypes
-import os
-import subprocess
-
 import numpy as np
 import pytest
 
 import train_inst_ref as tr
+from tests.simt.build import load, ptr as _p
 
-NAMES = ("ffb6d_last_error", "ffb6d_pose_targets", "ffb6d_pose_targets_inst", "ffb6d_pose_targets_inst_workspace_bytes")
 DTYPES = dict(labels=np.int32, inst_of_point=np.int32, kp_targ_ofst=np.float32, ctr_targ_ofst=np.float32, kp_3ds=np.float32,
               ctr_3ds=np.float32, n_points=np.int32)
 SENTINEL = 7
 
 
 @pytest.fixture(scope="module")
-def emu_inst(tmp_path_factory):
-    """errors.hip + train_data.hip + train_inst.hip compiled for the host against the emulator, with the flags of
-    tests/simt/build.py (train_data.hip for the comparison with ffb6d_pose_targets)."""
-    from ffb6d_amd import _lib
-    from tests.simt import build as sb
-    os.makedirs(sb.OUT, exist_ok=True)
-    out = str(tmp_path_factory.mktemp("simt_train_inst") / "libsimt_train_inst.so")
-    srcs = [sb.transformed(n) for n in ("errors.hip", "train_data.hip", "train_inst.hip")] + [os.path.join(sb.HERE, "simt.cpp")]
-    cmd = [sb.CLANG, "-x", "c++", "-std=c++17", "-O1", "-g", "-fPIC", "-shared", "-ffp-contract=off", "-Wno-unused-value",
-           "-Wno-psabi", "-Wno-unknown-attributes", "-I" + os.path.join(sb.HERE, "fake"), "-I" + sb.HERE,
-           "-I" + os.path.join(sb.ROOT, "include"), "-I" + sb.CSRC] + srcs + ["-o", out]
-    subprocess.run(cmd, check=True)
-    lib = ctypes.CDLL(out)
-    for name in NAMES:
-        fn = getattr(lib, name)
-        fn.restype, fn.argtypes = _lib.SIGNATURES[name]
-    return lib
-
-
-def _p(a):
-    return a.ctypes.data if a is not None else None
+def emu_inst():
+    """the emulated library (tests/simt/build.py)"""
+    return load()
 
 
 def emu_pose_targets(lib, cld, choose, label_img, cls_ids, RTs, kps, ctr):
