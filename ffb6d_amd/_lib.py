@@ -133,6 +133,16 @@ SIGNATURES = {
                                              _c.c_float, _i32, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "ffb6d_icp_refine_inst_f32": (_i32, [_vp, _i32, _i64, _vp, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i64,
                                          _c.c_float, _i32, _c.c_double, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "ffb6d_icp_normals_bytes": (_sz, [_i64]),
+    "ffb6d_icp_set_normals": (_i32, [_vp, _i64, _vp, _sz, _vp]),
+    "ffb6d_icp_estimate_normals_f32": (_i32, [_vp, _vp, _i32, _i64, _vp, _sz, _vp]),
+    "ffb6d_icp_plane_workspace_bytes": (_sz, [_i32, _i64]),
+    "ffb6d_icp_plane_inst_workspace_bytes": (_sz, [_i32, _i64, _i32]),
+    "ffb6d_icp_refine_plane_f32": (_i32, [_vp, _vp, _i32, _i64, _vp, _vp, _i32, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i64, _c.c_float,
+                                          _i32, _c.c_double, _i32, _c.c_double, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "ffb6d_icp_refine_plane_inst_f32": (_i32, [_vp, _vp, _i32, _i64, _vp, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i64,
+                                               _c.c_float, _i32, _c.c_double, _i32, _c.c_double, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
+                                               _sz, _vp]),
     # include/ffb6d_train.h
     "ffb6d_pose_targets": (_i32, [_vp, _vp, _i32, _vp, _i32, _vp, _vp, _i32, _vp, _vp, _i32, _i32, _i64, _i64, _i32, _i32, _vp,
                                   _vp, _vp, _vp, _vp, _vp, _vp, _vp]),

@@ -391,7 +391,9 @@ class ObjectInfo:
       corners f32 [n_cls,8,3], radius f32 [n_cls]; r_lst f32 [n_cls-1] = radius[1:], the reference's r_lst[cls_id - 1];
       kps_idx i32 [n_cls,n_kps]: the keypoints' vertex indices within their class (-1 for an empty class);
       models: an evaluate.ModelPoints of the FPS subset of n_model_points per class (refine.PreparedModels and evaluate take
-        it as it is), None when n_model_points is None.
+        it as it is), None when n_model_points is None.  With model_normals=True, models.normals holds one estimated unit
+        normal per model point (f32 [total,3]; refine.estimate_normals, the 16-neighbour rule of include/ffb6d_refine.h), so
+        refine.PreparedModels(info.models, normals=info.models.normals) serves the point-to-plane metric; None otherwise.
     Built by from_meshes, mesh_kps holds the texture-aware keypoints (the reference's use_orbfps) and kps_idx is None; then also
       fps_kps f32 [n_cls,n_kps,3]: the plain FPS keypoints of the vertices; n_found i32 [n_cls]: the lifted ORB points per class;
       textured: the TexturedPoints they were sampled from.  All three are None otherwise."""
@@ -404,10 +406,11 @@ class ObjectInfo:
         self.fps_kps = self.n_found = self.textured = None
 
     @classmethod
-    def from_points(cls, points, n_keypoints=8, n_model_points=None, start="center"):
+    def from_points(cls, points, n_keypoints=8, n_model_points=None, start="center", model_normals=False):
         """points: a render.PreparedMeshes or an evaluate.ModelPoints.  start="center" (the reference's init_center mode) is a
         deliberate departure from gen_obj_info.py, whose call leaves the start to `rand() % n` seeded from the clock: the same
-        mesh gives the same keypoints on every run.  Three launches (keypoints, box, model clouds) and no read-back."""
+        mesh gives the same keypoints on every run.  Three launches (keypoints, box, model clouds) and no read-back.
+        model_normals=True (needs n_model_points) also estimates the normals of the model clouds; that once waits for the device."""
         if not isinstance(points, (PreparedMeshes, ModelPoints)):
             raise TypeError(f"points must be a render.PreparedMeshes or an evaluate.ModelPoints, got {type(points).__name__}")
         n_keypoints = _samples(n_keypoints, "n_keypoints")
@@ -416,11 +419,18 @@ class ObjectInfo:
         s = _sets(points)
         idx, kps, _ = _fps(s, n_keypoints, start, False)
         corners, ctr, radius = box_info(points)
+        if model_normals and n_model_points is None:
+            raise ValueError("model_normals needs n_model_points: the normals belong to the model clouds")
         models = _model_points(s, n_model_points, start) if n_model_points is not None else None
+        if models is not None:
+            models.normals = None
+            if model_normals:
+                from .refine import estimate_normals
+                models.normals = estimate_normals(models)
         return cls(kps, ctr, corners, radius, idx, models)
 
     @classmethod
-    def from_meshes(cls, meshes, n_keypoints=8, n_model_points=None, keypoints="orb_fps", start="center", **views):
+    def from_meshes(cls, meshes, n_keypoints=8, n_model_points=None, keypoints="orb_fps", start="center", model_normals=False, **views):
         """Everything from_points gives, with mesh_kps = the FPS of the meshes' textured_points: what gen_obj_info.py writes as
         <name>_ORB_fps.txt and what use_orbfps selects downstream.  meshes: a render.PreparedMeshes or the list it takes;
         **views: textured_points' arguments (K, H, W, n1, n2, min_pixels, n_features, n_levels, fast_threshold, edge).
@@ -431,7 +441,7 @@ class ObjectInfo:
         if keypoints not in ("orb_fps", "fps"):
             raise ValueError(f'keypoints must be "orb_fps" or "fps", got {keypoints!r}')
         meshes = _prepared(meshes)
-        info = cls.from_points(meshes, n_keypoints, n_model_points, start)
+        info = cls.from_points(meshes, n_keypoints, n_model_points, start, model_normals)
         if keypoints == "fps":
             return info
         tex = textured_points(meshes, radius=info.radius, **views)

@@ -27,7 +27,8 @@ class SensorToPose:
     pose_inputs: optional callable (inp, out) -> (pcld [B,N,3], mask [B,N], ctr_of [B,1,N,3], kp_of [B,n_kps,N,3]) replacing the
     network's own votes (benchmarks with random weights feed a synthetic 5-object vote field; the stage still waits for the forward).
     refine: None, or the dict pose.solve_poses takes (models=refine.PreparedModels, max_iter, max_dist, ...): ICP refinement of the
-    fitted poses as the last step of stage C (on the pose side stream under the overlapped schedule).
+    fitted poses as the last step of stage C (on the pose side stream under the overlapped schedule); metric="plane" in the dict
+    (models prepared with normals) selects the point-to-plane metric, here and in instance_refine.
     max_instances: None = one pose per (frame, class) through pose.solve_poses (above); an integer K = stage C is
     pose.solve_instances: up to K scored instances per (frame, class), `solve` then returns its dict of device tensors (the rows
     bop.BOPSceneEval.add_batch takes).  Not with `refine` (that ICP selects its scene points by class).

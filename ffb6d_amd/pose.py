@@ -269,10 +269,11 @@ def solve_poses(pcld, mask, ctr_of, kp_of, mesh_kps, mesh_ctr, r_lst=None, use_c
                solved in every frame whether present or not (LineMOD flow: [1], :238-241);
       refine_mask: centre-clustering mask filter (:83-108); default = use_ctr_clus_flter and classes is None.
       stats: optional dict, receives the rounds made per set of each mean-shift pass.
-      refine: None, or dict(models=refine.PreparedModels, max_iter=..., max_dist=..., [tol, min_pairs]): the fitted poses of every
+      refine: None, or dict(models=refine.PreparedModels, max_iter=..., max_dist=..., [tol, min_pairs, metric, min_eig]): the fitted poses of every
               (frame, object) pair go through ONE refine.icp_refine call (ICP against the points of `pcld` that the `mask` given
               here assigns to the object) before they are read back; the keypoints column stays as fitted ("refine" in stats
-              receives the call's n_pairs / rms / iters).
+              receives the call's n_pairs / rms / iters).  metric="plane" (models prepared with normals) is the point-to-plane
+              metric of refine.icp_refine: fewer iterations for the same pose; "refine" in stats then also holds rms_plane.
     Returns a list over frames of (class_ids int array, poses [n,3,4] float64, kps [n,n_kps+1,3] float32);
     objects without points get the identity pose and zero keypoints (:114-117 / :239-240)."""
     _need_gpu(pcld, mask, ctr_of, kp_of)
@@ -388,7 +389,8 @@ def solve_instances(pcld, mask, ctr_of, kp_of, mesh_kps, mesh_ctr, max_instances
 def solve_instances_refined(pcld, mask, ctr_of, kp_of, mesh_kps, mesh_ctr, max_instances, refine=None, min_inside=1, min_fraction=0.0,
                             classes=None, use_ctr=True, radius=RADIUS, max_iter=300, stats=None, refine_mask=False, r_lst=None):
     """`solve_instances` with the two steps it leaves out, both instance-aware.  Arguments as solve_instances, and
-      refine: None, or dict(models=refine.PreparedModels, mode="nearest" | "map", max_iter=..., max_dist=..., [tol, min_pairs]):
+      refine: None, or dict(models=refine.PreparedModels, mode="nearest" | "map", max_iter=..., max_dist=..., [tol, min_pairs, metric,
+              min_eig]; metric="plane" needs models prepared with normals and takes fewer iterations, see refine.icp_refine):
               the fitted poses go through ONE refine.icp_refine_instances call with the instance map the solver has ("nearest",
               the default: the instances of a (frame, class) compete for every point of the class, also those whose centre vote
               fell in no cluster; "map": every instance keeps the points of its centre cluster).  The keypoints stay as fitted.

@@ -48,6 +48,44 @@
  * repeat a (frame, class, instance) in mode 0, or a (frame, class) in separate groups in mode 1, may keep the same point:
  * it then carries the id of either.
  *
+ * The point-to-plane metric (the *_plane calls; tests/icp_plane_ref.py restates what follows).  It minimises the distance of
+ * every scene point to the tangent plane at its model point, so a scene point may slide along the surface.  It needs one unit
+ * normal per model point, in a second buffer next to `prepared`, in the clouds' own order (ffb6d_icp_set_normals,
+ * ffb6d_icp_estimate_normals_f32).
+ *   Given normals: each is normalised once in double (n / sqrt(x*x + y*y + z*z)) and rounded to float32; a normal with a
+ *     non-finite component or of zero length becomes the zero vector.
+ *   Estimated normals: for model point j of class c take its k = min(16, n_c) nearest points of the class, itself included
+ *     (the exact search and tie rule of include/ffb6d_knn.h, ffb6d_knn_batch_device on the class's rows).  With p_i those points
+ *     in the order of the index row, in double from the float32 points: mean = (sum p_i) / k, C = sum (p_i - mean)(p_i - mean)^T.
+ *     The normal is the singular vector of C's smallest singular value (the cyclic one-sided Jacobi of the rigid fit: rotate
+ *     while |g_p . g_q| > 1.5 * 2^-52 |g_p| |g_q|; the first of equal values), normalised, with the sign that makes its
+ *     component of largest magnitude positive (the lowest axis wins ties), rounded to float32.  It is the zero vector when
+ *     n_c < 3 or the second singular value is zero (a point whose neighbours lie on a line or coincide).  The test is on
+ *     the computed value: neighbours on an axis-aligned line give exact zeros, neighbours on an oblique line may leave a
+ *     second value of rounding size (~2^-52 of the first), and the normal is then some unit vector across the line -- its
+ *     pairs pull along a direction the data does not determine.  Callers with such models pass mesh normals instead.
+ *   Class constants: c = the centre of the class's bounding box, rho = half its diagonal, in double from the float32 box
+ *     (c_a = (lo_a + hi_a) / 2, rho = sqrt(ex*ex + ey*ey + ez*ez) / 2).  Scaling by rho makes the rotation and the
+ *     translation columns of the system commensurate.
+ *   Steps 1-3 are the ones above, with the same bits for idx and d2 (in the instance calls: the mode's step 3).
+ *   4p. for every kept pair, in double from the float32 q (step 1), m = model[m(i)] and n = normal[m(i)]:
+ *         u = (q - c) / rho,   a = [u x n, n] in R^6,   r = n . (q - m) / rho
+ *       30 sums per block of 64 scene points, added in block order as in step 4 (no atomics): count, sum d2, sum r*r, the 21
+ *       upper entries of sum a a^T row by row, the 6 of sum a r.  A zero normal gives a zero row and still counts as a pair.
+ *   5p. M = sum a a^T, g = sum a r.  M is eigen-decomposed by cyclic two-sided Jacobi: the pair (p, q) is rotated while
+ *       |M_pq| > 1.5 * 2^-52 sqrt(M_pp M_qq) (false for NaN), at most 30 sweeps.  With l_max the largest eigenvalue,
+ *         x = - sum_k v_k (v_k . g) / l_k   over the k with l_k > 0 and l_k >= min_eig * l_max.
+ *       The directions left out are not moved: a plane keeps its in-plane pose, a sphere its rotation, a can its spin.
+ *       min_eig (0 <= min_eig < 1; 1e-6 in the Python calls) is a parameter of the method, not a tolerance of a test.
+ *       w = x[0:3], v = x[3:6]; Rd = exp([w]x) = I + A [w]x + B [w]x^2 with A = sin(th)/th, B = (1 - cos(th))/th^2, th = |w|;
+ *       below th = 1e-4, A = 1 - th^2/6 and B = 1/2 - th^2/24.  d = c - Rd c + rho v.   R <- R Rd^T, then t <- t - R_new d
+ *       (the scene point in the model frame moves from q to Rd q + d).
+ *       The problem ends with the pose it has when fewer than min_pairs pairs were kept, when rho = 0 (a class of one point or
+ *       none) or when x is not finite.  The stop rule is step 5's: max_iter, min_pairs, tol on the box corners.
+ *   Outputs as the point calls, and rms_plane f32 [P] = sqrt(rho^2 sum r*r / n) of the last iteration made, in metres, before
+ *   that iteration's update (0 without pairs).  A *_plane call with max_iter = 0 returns the input bits.
+ *   The point calls, their workspaces and their bits are what they were before the plane metric existed.
+ *
  * All pointers are DEVICE pointers unless stated; the ffb6d_icp_correspond* and ffb6d_icp_refine* calls enqueue their work
  * on `stream` and return without waiting for it or reading anything back.  Return value: 0 or an FFB6D_ERR_* code
  * (text through ffb6d_last_error()); on an error nothing is launched and no output is written.
@@ -139,6 +177,39 @@ int ffb6d_icp_refine_inst_f32(const void* prepared, int n_cls, int64_t total, co
                               int64_t set_stride, float max_dist, int max_iter, double tol, int min_pairs, int mode, double* T,
                               int* n_pairs, float* rms, int* iters, unsigned char* inst_out, void* workspace,
                               size_t workspace_bytes, ffb6d_stream_t stream);
+
+/* ---- the point-to-plane metric (the rule is stated at the top) ----------------------------------------------------------
+ * The normals buffer: ffb6d_icp_normals_bytes(total) bytes (0 when total < 0), float4 {nx, ny, nz, 0} per model point in
+ * the clouds' own order (the rows of model_pts).  Made once per model set by one of:
+ *   ffb6d_icp_set_normals: normals_in f32 [total,3] given by the caller (mesh vertex normals), validated, normalised and
+ *     copied on `stream`; it does not wait.
+ *   ffb6d_icp_estimate_normals_f32: estimated from the clouds alone (model_pts / model_begin as ffb6d_icp_prepare), one
+ *     exact K = min(16, n_c) search and one launch of icp_normals_kernel per class.  It reads model_begin back, allocates
+ *     its scratch and WAITS for `stream`, like ffb6d_icp_prepare.  total < 2^31. */
+size_t ffb6d_icp_normals_bytes(int64_t total);
+int ffb6d_icp_set_normals(const float* normals_in, int64_t total, void* normals, size_t normals_bytes, ffb6d_stream_t stream);
+int ffb6d_icp_estimate_normals_f32(const float* model_pts, const int64_t* model_begin, int n_cls, int64_t total, void* normals,
+                                   size_t normals_bytes, ffb6d_stream_t stream);
+
+/* The loops under the plane metric: the arguments of ffb6d_icp_refine_f32 / ffb6d_icp_refine_inst_f32, and
+ *   normals (the buffer above, after `prepared`), min_eig (after min_pairs), rms_plane f32 [P] or NULL (after rms);
+ *   workspace of ffb6d_icp_plane_workspace_bytes(P, set_stride) / ffb6d_icp_plane_inst_workspace_bytes(P, set_stride, mode)
+ *   bytes: the point calls' layout with 30 doubles per block of 64 scene points and one more row of state.
+ * The same number of launches per iteration as the point calls; no wait, no read-back.
+ * Refused with their own messages besides what the point calls refuse: normals == NULL, min_eig outside [0, 1). */
+size_t ffb6d_icp_plane_workspace_bytes(int P, int64_t set_stride);
+size_t ffb6d_icp_plane_inst_workspace_bytes(int P, int64_t set_stride, int mode);
+int ffb6d_icp_refine_plane_f32(const void* prepared, const void* normals, int n_cls, int64_t total, const float* pcld,
+                               const void* mask, int mask_bits, const unsigned char* keep, const int* frame_of,
+                               const int* class_of, const double* T0, int P, int B, int N, int64_t set_stride, float max_dist,
+                               int max_iter, double tol, int min_pairs, double min_eig, double* T, int* n_pairs, float* rms,
+                               float* rms_plane, int* iters, void* workspace, size_t workspace_bytes, ffb6d_stream_t stream);
+int ffb6d_icp_refine_plane_inst_f32(const void* prepared, const void* normals, int n_cls, int64_t total, const float* pcld,
+                                    const void* mask, int mask_bits, const unsigned char* keep, const unsigned char* inst,
+                                    const int* frame_of, const int* class_of, const int* inst_of, const double* T0, int P, int B,
+                                    int N, int64_t set_stride, float max_dist, int max_iter, double tol, int min_pairs,
+                                    double min_eig, int mode, double* T, int* n_pairs, float* rms, float* rms_plane, int* iters,
+                                    unsigned char* inst_out, void* workspace, size_t workspace_bytes, ffb6d_stream_t stream);
 
 #ifdef __cplusplus
 }
