@@ -334,7 +334,11 @@ class _UpsampleAlign(torch.autograd.Function):
                 rc = _lib.load().ffb6d_bilinear_bwd_pm(dt, g.data_ptr(), gin.data_ptr(), B, IH, IW, OH, OW, C, _stream(g))
             _lib.check(rc, "ffb6d_bilinear_bwd_pm")
             return gin, None
-        return torch.ops.aten.upsample_bilinear2d_backward(g, [OH, OW], list(ctx.in_shape), True, None, None), None
+        # ATen's device kernel adds every term onto the gradient with an atomic in the gradient's own type: a bf16 / fp16 map would
+        # be rounded after each of its up to ~(2 / ratio + 1)^2 terms (errors of percents where they cancel).  Sum in float32, round once.
+        g32 = g.float() if g.dtype in (torch.bfloat16, torch.float16) else g
+        gin = torch.ops.aten.upsample_bilinear2d_backward(g32, [OH, OW], list(ctx.in_shape), True, None, None)
+        return gin.to(g.dtype), None
 
 
 def upsample_align(x, size):
